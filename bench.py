@@ -2,6 +2,7 @@
 """bench.py — aircraft-steps/sec of the fused F-16 env.step on N MI355X GPUs of one node.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--n AIRCRAFT_PER_GPU] [--task heading|control|tracking|combat]
+                    [--dump-outputs DIR] [--full]
 
 `--gpus N` with N > 1 works as a plain command: when no launcher environment is present (WORLD_SIZE unset) the script
 re-executes itself under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1`, one rank
@@ -14,14 +15,20 @@ random actions from a fixed seed so that terminations / auto-resets occur at a r
 `--task tracking` is configs[3]'s per-GPU shape, `--task control` configs[2]'s stand-in, `--task combat` configs[4]
 (SingleCombat 1v1, engagements sharded by env, the opponent-observation all-gather inside the stepped loop).
 
-Protocol (the reference's own benchmark is envs/measure_env.py:65-78: back-to-back env.step, 500 steps, mean):
-  1. `cold_start`: reset, W warm-up steps, K timed steps — exactly the requested protocol from an idle GPU.  Reported, not `value`:
-     the MI355X clock governor needs ~50-100 ms of sustained load to reach its steady shader clock (2.07 -> 2.39 GHz measured with
-     the in-kernel counters, tools/microbench/cold_start.py), so an 8 ms window right after start-up measures the ramp.
-  2. `prelude`: untimed env.steps for --prelude-ms (default 300 ms) of GPU load, count reported.
-  3. W untimed warm-up steps, then EXACTLY K steps bracketed by barrier + synchronize on both sides, MAX over ranks -> `value`.
+Protocol of a plain run (the reference's own benchmark is envs/measure_env.py:65-78: back-to-back env.step, 500 steps, mean):
+  1. reset, then the `prelude`: untimed env.steps for about --prelude-ms (default 300 ms) of GPU load — the MI355X clock governor
+     needs ~50-100 ms of sustained load to reach its steady shader clock (2.07 -> 2.39 GHz measured with the in-kernel counters,
+     tools/microbench/cold_start.py).  In a one-process run their COUNT is a function of the arguments alone (nominal_step_s), so the
+     step index of every timed step, and with it every input of the run, is the same from run to run and from build to build.  With
+     --gpus N > 1 a step may hold collectives whose cost no constant knows: the count then comes from a measured W + K window
+     (`cold_start`, max over ranks, the same on every rank), and the step index of the timed steps may differ between runs.
+  2. W untimed warm-up steps, then EXACTLY K steps bracketed by barrier + synchronize on both sides, MAX over ranks -> `value`,
+     `ms_per_step` = that time / K.
+  3. `--dump-outputs DIR`: what the LAST timed step returned to its caller, as DIR/<name>.npy (float32; rank 0).
 Rank 0 prints `BENCH_DETAILS {...}` (everything measured) and then, LAST, the one contract JSON line (< 4 KB: metric, value,
-ms_per_step, config, roofline, cpu_baseline).  `--full` adds the side modes to the details (DESIGN.md §6 has the roofline arithmetic).
+ms_per_step, config, roofline).  A plain run does nothing else.  `--full` adds what is measured beside the headline: `cold_start` (the
+W + K window taken from the idle GPU, before the prelude), the effective shader clock (one more launch), `cpu_baseline` (on the contract
+line too), the loop breakdown and expected scaling of --task combat, and the side modes (DESIGN.md §6 has the roofline arithmetic).
 """
 import argparse
 import json
@@ -113,6 +120,35 @@ def cpu_baseline(task, budget_s=10.0, eager_budget_s=5.0):
             'reference_context': {'pytorch_cpu_8_vcpu_N1e5': 4.7e5, 'published_pytorch_cuda_N1e6': 4.75e6, 'unit': 'aircraft-steps/s'}}
 
 
+def nominal_step_s(task, solver, rows):
+    """Step time used ONLY to size the prelude (steps = prelude_ms / this): a constant of the workload's arguments — 0.3 ns per aircraft
+    and Euler step (3.4e9 aircraft-steps/s), three times that for rk4, 3 ns per SingleCombat engagement (0.36 ms at 1e5),
+    never below the 25 us of a launch-bound step — and not a measurement, so that the number of steps before the timed ones is fixed."""
+    per_row = 3.0e-9 if task == 'combat' else 0.9e-9 if solver == 'rk4' else 0.3e-9
+    return max(25e-6, rows * per_row)
+
+
+DUMP_MAX_BYTES = 60 * 2 ** 20
+
+
+def dump_outputs(path, named):
+    """--dump-outputs: the tensors the last timed step handed to its caller -> <path>/<name>.npy, float32 (masks as 0 / 1), row-major
+    [rows, ...].  Above DUMP_MAX_BYTES in total the SAME fixed sample of rows (numpy RandomState(0), sorted) is kept of every array."""
+    import numpy as np
+    total = sum(4 * t.numel() for t in named.values())
+    frac = min(1.0, DUMP_MAX_BYTES / max(1, total))
+    os.makedirs(path, exist_ok=True)
+    shapes = {}
+    for name, t in named.items():
+        a = t.detach().to('cpu').numpy()
+        if frac < 1.0:    # arrays of equal length get the same rows: same seed, same draw
+            a = a[np.sort(np.random.RandomState(0).choice(a.shape[0], max(1, int(a.shape[0] * frac)), replace=False))]
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        np.save(os.path.join(path, name + '.npy'), a)
+        shapes[name] = {'rows_written': int(a.shape[0]), 'rows': int(t.shape[0])}
+    return {'dir': path, 'arrays': shapes}
+
+
 def free_port():
     s = socket.socket()
     s.bind(('127.0.0.1', 0))
@@ -174,21 +210,31 @@ class Timer:
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         self.barrier()
         t0 = time.perf_counter()
+        self.last = None                          # what the LAST timed step returned (--dump-outputs); only that one is held
         if self.per_launch:
-            for _ in range(steps):
+            for _ in range(steps - 1):
                 self.step(i)
+                i += 1
+            if steps > 0:
+                self.last = self.step(i)
                 i += 1
         else:
             # launch 1 of K carries its own event pair (the GPU idles for the host's first-call latency before it, which is
             # not kernel time); ONE pair spans launches 2..K.  average launch duration = (d_1 + span_2..K) / K
             self.batch.set_timing(True)
-            if steps > 0:
+            if steps == 1:
+                self.last = self.step(i)
+                i += 1
+            elif steps > 1:
                 self.step(i)
                 i += 1
             self.batch.set_timing(False)
             ev0.record()
-            for _ in range(max(0, steps - 1)):
+            for _ in range(max(0, steps - 2)):
                 self.step(i)
+                i += 1
+            if steps > 1:
+                self.last = self.step(i)
                 i += 1
             ev1.record()
         host_enqueue = time.perf_counter() - t0   # this rank's host time to enqueue the K steps (before it waits for the GPU)
@@ -335,15 +381,22 @@ def run_env(args, rank, local_rank, world, dev, dist):
     tm = Timer(lambda i: env.step(pool[i % len(pool)]), b, dev, dist, args.backend)
 
     env.reset()
-    cold_el, cold_samples, i = tm.window(args.warmup, args.steps)            # 1. the requested protocol from an idle GPU
-    p_steps, p_sec, i = tm.prelude(args.prelude_ms * 1e-3, i, est_step_s=cold_el / max(1, args.steps))   # 2. clock-governor ramp, untimed, reported
-    elapsed, samples, i = tm.window(args.warmup, args.steps, i)              # 3. W warm-up + EXACTLY K timed steps -> value
-    mhz = shader_mhz(b, lambda k: env.step(pool[0]), n, dev) if rank == 0 else None
+    cold = args.full or world > 1     # the requested protocol from an idle GPU: beside the headline (--full); several ranks size their prelude by it
+    cold_el, cold_samples, i = tm.window(args.warmup, args.steps) if cold else (None, None, 0)
+    est = cold_el / max(1, args.steps) if world > 1 else nominal_step_s(args.task, args.solver, n)
+    p_steps, p_sec, i = tm.prelude(args.prelude_ms * 1e-3, i, est_step_s=est)   # clock-governor ramp, untimed, reported
+    elapsed, samples, i = tm.window(args.warmup, args.steps, i)              # W warm-up + EXACTLY K timed steps -> value
+    dumped = None
+    if args.dump_outputs and rank == 0 and tm.last is not None:
+        obs, reward, done, bad_done, exceed_time_limit = tm.last[:5]         # BaseEnv.step's return value without the info dict
+        dumped = dump_outputs(args.dump_outputs, {'obs': obs, 'reward': reward, 'done': done, 'bad_done': bad_done, 'exceed_time_limit': exceed_time_limit})
+    tm.last = None
+    mhz = shader_mhz(b, lambda k: env.step(pool[0]), n, dev) if rank == 0 and args.full else None
     mem_mb = torch.cuda.max_memory_allocated(dev) / 2 ** 20   # env state + cache + outputs of one step + the 8-entry action pool
     fin = bool(torch.isfinite(env.model.s).all().item())       # sanity of the timed region: states finite
     if rank != 0:
         return None
-    st, cst = stats(samples), stats(cold_samples)
+    st, cst = stats(samples), stats(cold_samples) if cold else None
     kern_s = st['kernel_avg_ms'] * 1e-3
     flop = ALGO_FLOP_RK4 if args.solver == 'rk4' else ALGO_FLOP
     ach_tflops = n * flop / kern_s / 1e12 if kern_s > 0 else 0.0
@@ -366,9 +419,10 @@ def run_env(args, rank, local_rank, world, dev, dist):
         'expected_scaling': expected_weak_scaling(tm.rank_host_us_per_step[0], 1e3 * elapsed / args.steps, st['kernel_avg_ms'], world),
         'prelude': {'steps': p_steps, 'seconds': p_sec, 'timed': False,
                     'why': 'clock-governor ramp: the shader clock reaches its steady state only after ~50-100 ms of load '
-                           '(cold_start below is the same K-step window taken from an idle GPU)'},
-        'cold_start': {'value': world * n * args.steps / cold_el, 'ms_per_step': 1e3 * cold_el / args.steps, **cst,
-                       'note': 'reset + W warm-up + K timed steps from an idle GPU, before the prelude; not the headline'},
+                           '(cold_start, with --full, is the same K-step window taken from an idle GPU); one process: the count is fixed by the arguments'},
+        **({'cold_start': {'value': world * n * args.steps / cold_el, 'ms_per_step': 1e3 * cold_el / args.steps, **cst,
+                           'note': 'reset + W warm-up + K timed steps from an idle GPU, before the prelude; not the headline'}} if cold else {}),
+        **({'dumped_outputs': dumped} if dumped else {}),
         'roofline': {'bound': 'valu', 'achieved': ach_tflops, 'peak': PEAK_FP32_TFLOPS, 'unit': 'TFLOP/s',
                      'frac': ach_tflops / PEAK_FP32_TFLOPS,
                      'traffic': traffic, 'traffic_source': traffic_src,
@@ -693,19 +747,31 @@ def run_combat(args, rank, local_rank, world, dev, dist):
     def step(i):
         if args.interleaved:   # round-2 loop, kept for A/B: interleaved [2E, .] rows, torch split / contiguous / stack around the launch
             a = ex.actions(state['obs'], ego_policy)
-            state['obs'] = cenv.step(a)[0]
+            r = cenv.step(a)
+            state['obs'] = r[0]
         else:
             ea, oa = ex.actions_split(state['obs'][0], state['obs'][1], ego_policy)
-            state['obs'] = cenv.step_split(ea, oa)[:2]
+            r = cenv.step_split(ea, oa)
+            state['obs'] = r[:2]
+        return r
 
     tm = Timer(step, cenv._batch, dev, dist, args.backend, per_launch=True)
-    cold_el, cold_samples, i = tm.window(args.warmup, args.steps)
-    p_steps, p_sec, i = tm.prelude(args.prelude_ms * 1e-3, i, est_step_s=cold_el / max(1, args.steps))   # same count on every rank: steps hold collectives
+    cold = args.full or world > 1     # as in run_env; a step of several ranks holds collectives, whose cost no constant knows: measured there
+    cold_el, cold_samples, i = tm.window(args.warmup, args.steps) if cold else (None, None, 0)
+    est = cold_el / max(1, args.steps) if world > 1 else nominal_step_s('combat', None, e_total)
+    p_steps, p_sec, i = tm.prelude(args.prelude_ms * 1e-3, i, est_step_s=est)   # same count on every rank (cold_el is the max over ranks)
     elapsed, samples, i = tm.window(args.warmup, args.steps, i)
+    dumped = None
+    if args.dump_outputs and rank == 0 and tm.last is not None:      # rank 0's shard, as SingleCombatEnv.step / step_split returned it (no info dict)
+        names = ('obs', 'reward', 'done', 'bad_done', 'exceed_time_limit') if args.interleaved else \
+                ('obs_ego', 'obs_opp', 'reward', 'done', 'bad_done', 'exceed_time_limit')
+        dumped = dump_outputs(args.dump_outputs, dict(zip(names, tm.last)))
+    tm.last = None
     fin = bool(torch.isfinite(cenv.s).all().item())
-    plain_ms = 1e3 * _wall(step, cenv._batch, dev, 10, max(50, args.steps)) if world == 1 else None   # the loop without timing events
+    extras = world == 1 and args.full                                 # the loop taken apart: runs of their own, beside the headline
+    plain_ms = 1e3 * _wall(step, cenv._batch, dev, 10, max(50, args.steps)) if extras else None   # the loop without timing events
     policy_ms = None
-    if world == 1 and not args.interleaved:   # the two stand-in policies alone (4 small torch kernels): what the loop spends outside this library
+    if extras and not args.interleaved:   # the two stand-in policies alone (4 small torch kernels): what the loop spends outside this library
         oe, oo = state['obs']
         ids = torch.arange(e_loc, device=dev)
         policy_ms = 1e3 * _wall(lambda i: (ego_policy(oe), opp_policy(oo, ids)), cenv._batch, dev, 10, 200)
@@ -761,7 +827,8 @@ def run_combat(args, rank, local_rank, world, dev, dist):
         'stand_in_policies_ms': policy_ms,
         'exchange_and_glue_ms': (plain_ms - st['kernel_avg_ms'] - policy_ms) if (plain_ms is not None and policy_ms is not None) else None,
         'prelude': {'steps': p_steps, 'seconds': p_sec, 'timed': False},
-        'cold_start': {'value': e_total * args.steps / cold_el, 'ms_per_step': 1e3 * cold_el / args.steps, **stats(cold_samples)},
+        **({'cold_start': {'value': e_total * args.steps / cold_el, 'ms_per_step': 1e3 * cold_el / args.steps, **stats(cold_samples)}} if cold else {}),
+        **({'dumped_outputs': dumped} if dumped else {}),
         'roofline': {'bound': 'valu', 'achieved': ach, 'peak': PEAK_FP32_TFLOPS, 'unit': 'TFLOP/s', 'frac': ach / PEAK_FP32_TFLOPS,
                      'algorithmic_flop_per_engagement_step': 2 * 5 * ALGO_FLOP_COMBAT_FDM, 'kernel': 'f16_combat_kernel<solver,STEP>', **st,
                      'traffic': None, 'note': 'rank 0 kernel; per engagement-step 2 aircraft x 5 FDM steps x 34.1 KFLOP'},
@@ -836,10 +903,14 @@ def main():
                          'so that the exchange overlaps the env kernel')
     ap.add_argument('--prelude-ms', type=float, default=300.0, help='untimed GPU load before the timed window (clock-governor ramp); 0 disables')
     ap.add_argument('--headline-only', '--no-cpu-baseline', dest='headline_only', action='store_true',
-                    help='skip cpu_baseline and the optional modes reported beside the headline')
+                    help='with --full: skip cpu_baseline and the optional modes reported beside the headline (a plain run has neither)')
     ap.add_argument('--full', action='store_true',
-                    help='also run the modes reported beside the headline (rk4, 1-D tables, N = 1e7, N = 256 latency, SingleCombat, PlanningEnv, the collect '
-                         'loop, the reference protocol): minutes, reported on the BENCH_DETAILS line / gpurun_out/bench_details.json, never on the contract line')
+                    help='also measure what is reported beside the headline: cold_start, the effective shader clock, cpu_baseline, the loop breakdown of '
+                         '--task combat and the side modes (rk4, 1-D tables, N = 1e7, N = 256 latency, SingleCombat, PlanningEnv, the collect loop, the '
+                         'reference protocol): minutes; all but cpu_baseline on the BENCH_DETAILS line / in the details file only, never on the contract line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the LAST timed step returned to its caller (observation, reward, the three masks) as '
+                         'DIR/<name>.npy, float32; above 60 MB in total a fixed seeded sample of the rows.  One process: same arguments -> same inputs')
     ap.add_argument('--backend', default='nccl', choices=['nccl', 'gloo'],
                     help="torch.distributed backend: 'nccl' = RCCL (default); 'gloo' lets the multi-rank path be exercised on a box with "
                          'fewer GPUs than ranks (ranks then share GPUs: a functional check, not a benchmark)')
@@ -869,7 +940,7 @@ def main():
     else:
         out = run_env(args, rank, local_rank, world, dev, dist)
     if rank == 0:
-        if world == 1 and not args.headline_only:
+        if world == 1 and args.full and not args.headline_only:
             out['cpu_baseline'] = cpu_baseline('heading' if args.task == 'combat' else args.task)
         emit(out)
     if dist is not None:

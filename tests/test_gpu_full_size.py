@@ -215,7 +215,7 @@ def test_bench_multi_rank_path_on_one_gpu():
     torch.distributed.run, one process per rank — here with the gloo backend so that two ranks can share this box's single GPU:
     sharding, barrier, max-over-ranks and the rank-0 JSON line of the weak-scaling path are exercised on real hardware (RCCL
     itself is not)."""
-    d = _bench_json(['--gpus', '2', '--steps', '20', '--warmup', '3', '--n', '200000', '--backend', 'gloo', '--prelude-ms', '50'])
+    d = _bench_json(['--gpus', '2', '--steps', '20', '--warmup', '3', '--n', '200000', '--backend', 'gloo', '--prelude-ms', '50', '--full'])
     assert d['n_gpus'] == 2 and d['world_size'] == 2 and d['steps'] == 20 and d['scaling'] == 'weak' and d['state_finite'] is True
     assert d['backend'] == 'gloo' and d['rccl_ranks'] == 0
     assert d['value'] == pytest.approx(2 * 200000 * 20 / (d['ms_per_step'] * 1e-3 * 20), rel=1e-6)
@@ -224,7 +224,7 @@ def test_bench_multi_rank_path_on_one_gpu():
 
 
 def test_bench_single_gpu_line_has_the_contract_fields():
-    d = _bench_json(['--steps', '20', '--warmup', '5', '--n', '100000', '--headline-only', '--prelude-ms', '50'])
+    d = _bench_json(['--steps', '20', '--warmup', '5', '--n', '100000', '--full', '--headline-only', '--prelude-ms', '50'])
     for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling', 'vs_baseline', 'dtype',
               'data', 'config', 'roofline'):
         assert k in d, k
@@ -238,21 +238,72 @@ def test_bench_single_gpu_line_has_the_contract_fields():
     assert d['expected_scaling']['host_keeps_gpu_fed'] in (True, False) and d['expected_scaling']['measured_at_world_size'] == 1
 
 
-def test_bench_driver_command_last_line_is_the_small_contract_line():
-    """The driver's own command (`bench.py --gpus 1 --steps 20 --warmup 5`, full size, CPU baselines included): the LAST stdout line is
-    the contract line and nothing else — < 4 KB (round 5's 28.8 KB line was not parsed), json.loads succeeds, it carries value,
-    ms_per_step, roofline.frac and cpu_baseline.value, K x ms_per_step fits inside the run's wall time, and the run stays under 60 s
-    (40 s is the target on a warm box; the first `import torch` of a fresh one takes longer)."""
-    d, line, wall = _bench_json(['--gpus', '1', '--steps', '20', '--warmup', '5'], raw=True)
+def test_bench_driver_command_last_line_is_the_small_contract_line(tmp_path):
+    """The driver's own command (`bench.py --gpus 1 --steps 20 --warmup 5`, full size, a plain run, here with --dump-outputs): the LAST
+    stdout line is the contract line and nothing else — < 4 KB (round 5's 28.8 KB line was not parsed), json.loads succeeds, it carries
+    value, ms_per_step and roofline.frac, K x ms_per_step fits inside the run's wall time.  A plain run measures nothing beside the
+    headline (no cpu_baseline, cold_start, shader-clock launch or side mode) and spends under 30 s outside its W + K steps, start of the
+    interpreter to exit; the dump is float32, at most 64 MB, the same rows of every array."""
+    out = tmp_path / 'dump'
+    d, line, wall = _bench_json(['--gpus', '1', '--steps', '20', '--warmup', '5', '--dump-outputs', str(out)], raw=True)
     assert set(line) >= {'metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling', 'vs_baseline',
-                         'dtype', 'data', 'config', 'roofline', 'cpu_baseline'}
+                         'dtype', 'data', 'config', 'roofline'}
     assert line['metric'].startswith('aircraft-steps/sec at N=1e6 F-16 Heading') and line['config']['aircraft_per_gpu'] == 1_000_000
     assert line['value'] == pytest.approx(1_000_000 * 20 / (line['ms_per_step'] * 1e-3 * 20), rel=1e-6) and line['value'] > 1e9
-    r, c = line['roofline'], line['cpu_baseline']
+    assert line['unit'] == 'aircraft-steps/s' and line['higher_is_better'] is True and line['dtype'] == 'f32' and line['steps'] == 20
+    r = line['roofline']
     assert 0.3 < r['frac'] < 1.0 and r['executed_frac'] < r['frac'] and r['kernel_avg_ms'] <= line['ms_per_step'] * 1.001
     assert r['algorithmic_bytes_per_launch'] == 278.0 * 1_000_000 and (r['traffic'] is None or r['traffic'] >= r['algorithmic_bytes_per_launch'])
+    assert r['launches_timed'] == 20 and d['prelude']['steps'] == 1000          # 300 ms / the nominal 0.3 ms: fixed by the arguments
+    for k in ('cpu_baseline', 'cold_start', 'optional_modes'):
+        assert k not in d and k not in line, k
+    assert r.get('effective_shader_mhz') is None
+    assert wall - 25 * line['ms_per_step'] * 1e-3 < 30, wall
+    files = sorted(p.name for p in out.iterdir())
+    assert files == ['bad_done.npy', 'done.npy', 'exceed_time_limit.npy', 'obs.npy', 'reward.npy']
+    arrs = {f: np.load(out / f) for f in files}
+    rows = arrs['obs.npy'].shape[0]
+    assert 500_000 < rows < 1_000_000 and arrs['obs.npy'].shape == (rows, 22)
+    assert all(a.dtype == np.float32 and a.shape[0] == rows for a in arrs.values())
+    assert 32 * 2 ** 20 < sum(a.nbytes for a in arrs.values()) <= 64 * 10 ** 6
+    assert np.isfinite(arrs['obs.npy'][arrs['bad_done.npy'] == 0]).all() and set(np.unique(arrs['done.npy'])) <= {0.0, 1.0}
+
+
+def test_bench_dump_outputs_is_the_last_timed_step_of_a_reproducible_run(tmp_path):
+    """--dump-outputs writes what the LAST timed env.step returned, and the run's inputs depend on its arguments alone: the same reset,
+    the same action pool (generator seed 1234 + rank) and the same number of steps — prelude (a count fixed by the arguments) + W + K —
+    replayed in this process give the dumped arrays bit for bit.  Below the size limit every row is written."""
+    n, k, w = 20_000, 7, 3
+    out = tmp_path / 'dump'
+    d = _bench_json(['--steps', str(k), '--warmup', str(w), '--n', str(n), '--prelude-ms', '5', '--dump-outputs', str(out)])
+    assert d['steps'] == k and d['roofline']['launches_timed'] == k and d['prelude']['steps'] == 200     # 5 ms / the 25 us floor
+    total = d['prelude']['steps'] + w + k
+    env = _env('heading', n, 0)
+    g = torch.Generator(device='cuda:0')
+    g.manual_seed(1234)
+    pool = [torch.rand((n, 4), generator=g, device='cuda:0') * 2 - 1 for _ in range(8)]
+    env.reset()
+    for i in range(total):
+        ret = env.step(pool[i % 8])
+    for name, t in zip(('obs', 'reward', 'done', 'bad_done', 'exceed_time_limit'), ret):
+        a = np.load(out / (name + '.npy'))
+        assert a.dtype == np.float32 and a.shape == tuple(t.shape)
+        assert np.array_equal(a, t.cpu().numpy().astype(np.float32), equal_nan=True), name
+    assert np.load(out / 'done.npy').sum() + np.load(out / 'bad_done.npy').sum() > 0      # terminations are in the sample
+
+
+def test_bench_full_reports_the_cpu_baselines_and_the_side_modes():
+    """`--full`: everything measured beside the headline is still measured — cold_start, the shader clock, cpu_baseline (on the contract
+    line too: the C port of the reference path and the eager-PyTorch formulation on the host cores) and the side modes — and the contract
+    line stays the small last line."""
+    d, line, wall = _bench_json(['--gpus', '1', '--steps', '20', '--warmup', '5', '--n', '100000', '--prelude-ms', '50', '--full'], timeout=600, raw=True)
+    c = line['cpu_baseline']
     assert c['value'] > 0 and c['cores'] >= 1 and c['kind'] == 'port' and 'oracle/f16_oracle.c' in c['sample'] and c['torch_eager'] > 0
-    assert 'optional_modes' not in d and wall < 60, wall
+    assert d['cold_start']['launches_timed'] == 20 and 1500 < line['roofline']['effective_shader_mhz'] < 2600
+    assert set(d['optional_modes']) >= {'aero_1d_tables', 'solver_rk4', 'latency_n256', 'singlecombat_1v1', 'planning_tracking_n8192',
+                                        'planning_tracking_n1e4', 'planning_tracking_n262144', 'collect_loop_n3000', 'collect_loop_n1e4',
+                                        'reference_protocol'}
+    assert 'optional_modes' not in line and wall < 600, wall
 
 
 @pytest.mark.parametrize('task', ['tracking', 'combat'])

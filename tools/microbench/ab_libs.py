@@ -35,7 +35,7 @@ def main():
     for _ in range(args.rounds):
         for n in names:
             env = dict(os.environ, NPF16_LIB=os.path.join(LIBS, n + '.so'))
-            cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--headline-only', '--steps', str(args.steps), '--warmup', '5', '--n', str(args.n),
+            cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--headline-only', '--steps', str(args.steps), '--warmup', '5', '--n', str(args.n),
                    '--task', args.task] + args.extra.split()
             r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
             # bench.py prints everything it measured on the BENCH_DETAILS line and the small contract line last (round 6)

@@ -12,7 +12,6 @@ __global__ void chase(const int* __restrict__ ring, int steps, long long* out, i
         // the ring is sequential with stride 64 B: the line 8 entries ahead is known
         const int* ahead = ring + ((idx + 8 * 16) & (64 * 1024 / 4 * 16 - 1));
         if (MODE == 1) asm volatile("s_atc_probe 0x0, %0, 0x0" ::"s"(ahead));
-        if (MODE == 2) asm volatile("s_dcache_discard %0, 0x0" ::"s"(ahead));
         // ~200 cycles of unrelated scalar work so that a prefetch has time to land
         int acc = idx;
 #pragma unroll
