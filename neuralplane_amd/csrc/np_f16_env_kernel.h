@@ -415,6 +415,7 @@ void f16_env_kernel(const KArgs a) {
         float xd[12];
 #if defined(NPF16_EXP) && (NPF16_EXP & 2)  // timing experiment only: no Overload evaluation
         for (int k = 0; k < 12; k++) xd[k] = s[k];
+        pow_new = atmos_pow(ap->cfg.af, s[2]);
 #else
         {
             const AeroWeights wt2 = {ap->wt.kblob, ap->wt.kblob_dual, ap->wt.pwl, ap->wt.pwl_unnorm};
@@ -522,7 +523,10 @@ void f16_env_kernel(const KArgs a) {
     if constexpr (!SHARED) {
         NP_REREAD_ARGS(ap);
         if (!INNER || ap->obs) {  // an intermediate inner iteration of PlanningEnv.step may not want the task observation at all
-        observe<TASK>(ap->cfg, s, u, tgt, tr, o);
+        // A step already has (1 - 0.703e-5 alt)^4.14 of the state it reached: its Overload evaluation computed it for the air density.  EAS2TAS
+        // takes that value instead of running the fp64 pow sequence on the same altitude a second time (same bits: observe<.., HAVE_POW>).
+        if constexpr (STEP) observe<TASK, true>(ap->cfg, s, u, tgt, tr, o, pow_new);
+        else observe<TASK>(ap->cfg, s, u, tgt, tr, o);
         if (ap->noise) {  // obs + randn_like(obs) * noise_scale
 #pragma unroll
             for (int k = 0; k < 22; k++) o[k] = o[k] + ap->noise[ic * 22 + k] * ap->cfg.noise_scale;
@@ -593,6 +597,7 @@ void f16_env_kernel(const KArgs a) {
 #pragma unroll
                 for (int k = 0; k < 3; k++) t3[k] = at_off(ap->ll_tgt + k * ap->ld, o4);
                 if constexpr (SHARED) observe<1, true>(ap->cfg, s, u, t3, tr, o2, sc1.powv);
+                else if constexpr (STEP) observe<1, true>(ap->cfg, s, u, t3, tr, o2, pow_new);
                 else observe<1>(ap->cfg, s, u, t3, tr, o2);
             }
             store_rows22(ap->ll_obs, o2);

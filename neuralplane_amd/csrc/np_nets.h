@@ -90,6 +90,8 @@ constexpr int NUM_CACHED = 14;     // force-side alpha/beta-only nets: the first
 // sine / cosine sequences and one pow).  It removes 269 of 8 747 VALU instructions per wave (-3.1 %) for 80 B more traffic per
 // aircraft-step — and is SLOWER: +0.6 % at N = 1e6, +1.2 % at 1e7, +9..+47 % on one-generation grids (98 304 - 262 144), where the ten
 // extra loads in front of the first instruction and the longer store burst are not hidden.  Bit-identical either way (351 GPU tests).
+// Round 7: with the loads moved BEHIND the integrator's net phase and keys for phi, theta and the altitude it is still +1.9 % at N = 1e6
+// (profiles/r07_pow_reuse/ab_headline_trig_carry_late_load.log); the supposed cause, not measured, is the 104 B more traffic per aircraft-step.
 #ifndef NPF16_TRIG_CACHE
 #define NPF16_TRIG_CACHE 0
 #endif
