@@ -81,7 +81,13 @@ typedef struct np_f16_cfg {
      * Same functions (a ReLU MLP of one input IS piecewise linear), 0.4 ppm from their fp64 value; results
      * differ from the default by ~1e-5 relative per coefficient, i.e. by the fp32 noise of the MLP itself. */
     int32_t aero_1d_tables;
-    int32_t reserved_cfg_;
+    /* Numerics option (not a reference key; was a reserved word, 0 keeps its meaning): evaluate every Linear layer of the 43 aero MLPs
+     * in GEMM order — acc = W[j][0] x[0]; acc = fma(W[j][k], x[k], acc), k ascending; then acc + bias[j]; plain ReLU; the output layer
+     * as ONE chain — the order of the reference's nn.Linear (a dot product with a bias epilogue) instead of the default's bias-first
+     * chains.  2-4 x closer to the reference's trajectories; single-set kernels only: np_f16_step / np_f16_reset
+     * (throughput and latency variants; NP_KERNEL_PAIR is refused), np_f16_aero_coefficients, np_f16_derived; np_planning_inner_loop runs
+     * launch by launch.  Excludes aero_1d_tables. */
+    int32_t aero_gemm_order;
     np_f16_airframe airframe;   /* all zero = the F-16 literals (see np_f16_airframe) */
 } np_f16_cfg;
 
@@ -251,7 +257,7 @@ typedef struct np_f16_combat_cfg {
     double roll_ff, gravity;           /* pitchcontroller.yaml */
     double airspeed_min, airspeed_max; /* controller.py:15 */
     int32_t aero_1d_tables;            /* see np_f16_cfg.aero_1d_tables */
-    int32_t reserved_cfg_;
+    int32_t aero_gemm_order;           /* see np_f16_cfg.aero_gemm_order; SingleCombat has no such kernels: must be 0 (was a reserved word) */
     np_f16_airframe airframe;          /* all zero = the F-16 literals */
 } np_f16_combat_cfg;
 
@@ -476,6 +482,11 @@ typedef struct np_dispatch_info {
     int32_t planning_mode_i8; /* ABI 15 (was reserved): the same with the block-fixed-point controller weights (no dual workgroups: queue / guests there) */
 } np_dispatch_info;
 int np_dispatch_plan(int64_t n, int32_t num_cus, int32_t step, int32_t solver, int32_t tables, int32_t variant, np_dispatch_info *out);
+/* The same for a context with cfg.aero_gemm_order: never the pair family, planning_mode = NP_PLANNING_LAUNCHES; variant = NP_KERNEL_PAIR fails. */
+int np_dispatch_plan_gemm(int64_t n, int32_t num_cus, int32_t step, int32_t solver, int32_t variant, np_dispatch_info *out);
+/* The weight records a context with cfg.aero_gemm_order uploads (bias rows behind their weight rows; csrc/np_nets.h::gemm_record_len), packed
+ * on the host — no device needed.  Returns the number of floats (out may be NULL to ask for it), -1 on a bad blob or a short buffer. */
+int64_t np_f16_pack_kblob_gemm(const void *weights_blob, size_t nbytes, float *out, int64_t cap);
 
 /* Average duration in ms of the `count` most recent np_f16_step / np_f16_combat_step launches on this context, measured with
  * HIP events on the launch stream: a start / stop pair attached to each kernel's own dispatch (hipExtLaunchKernelGGL — the

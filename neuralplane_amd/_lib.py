@@ -61,7 +61,7 @@ class NpF16Cfg(C.Structure):
                 ('max_heading_increment', C.c_double), ('max_pitch_increment', C.c_double),
                 ('max_velocities_u_increment', C.c_double),
                 ('max_distance', C.c_double), ('min_distance', C.c_double),
-                ('aero_1d_tables', C.c_int32), ('reserved_cfg_', C.c_int32), ('airframe', NpF16Airframe)]
+                ('aero_1d_tables', C.c_int32), ('aero_gemm_order', C.c_int32), ('airframe', NpF16Airframe)]
 
 
 class NpF16Io(C.Structure):
@@ -92,7 +92,7 @@ class NpF16CombatCfg(C.Structure):
                 ('max_epos', C.c_double), ('min_epos', C.c_double),
                 ('roll', NpPidGains), ('pitch', NpPidGains), ('yaw', NpPidGains),
                 ('roll_ff', C.c_double), ('gravity', C.c_double), ('airspeed_min', C.c_double), ('airspeed_max', C.c_double),
-                ('aero_1d_tables', C.c_int32), ('reserved_cfg_', C.c_int32), ('airframe', NpF16Airframe)]
+                ('aero_1d_tables', C.c_int32), ('aero_gemm_order', C.c_int32), ('airframe', NpF16Airframe)]
 
 
 class NpPlanningLoop(C.Structure):
@@ -117,18 +117,39 @@ class NpDispatchInfo(C.Structure):
                                           'combat_latency')] + [('grid', C.c_int64), ('planning_mode', C.c_int32), ('planning_mode_i8', C.c_int32)]
 
 
-def dispatch_plan(n, num_cus, step=True, solver=0, tables=False, variant=0):
-    """np_dispatch_plan as a dict: the variant / tiling / row-group selection for n rows on a device with num_cus CUs (no GPU needed)."""
+def dispatch_plan(n, num_cus, step=True, solver=0, tables=False, variant=0, gemm_order=False):
+    """np_dispatch_plan as a dict: the variant / tiling / row-group selection for n rows on a device with num_cus CUs (no GPU needed).
+    gemm_order: the plan of a context with aero_gemm_order (np_dispatch_plan_gemm: single-set kernels only, never the pair family)."""
     info = NpDispatchInfo()
     lib = load()
-    lib.np_dispatch_plan.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(NpDispatchInfo)]
-    check(lib.np_dispatch_plan(int(n), int(num_cus), int(bool(step)), int(solver), int(bool(tables)), int(variant), C.byref(info)))
+    if gemm_order:
+        if tables:
+            raise ValueError('aero_gemm_order and aero_1d_tables exclude each other')
+        lib.np_dispatch_plan_gemm.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(NpDispatchInfo)]
+        check(lib.np_dispatch_plan_gemm(int(n), int(num_cus), int(bool(step)), int(solver), int(variant), C.byref(info)))
+    else:
+        lib.np_dispatch_plan.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(NpDispatchInfo)]
+        check(lib.np_dispatch_plan(int(n), int(num_cus), int(bool(step)), int(solver), int(bool(tables)), int(variant), C.byref(info)))
     return {k: getattr(info, k) for k, _ in NpDispatchInfo._fields_ if k != 'reserved_'}
+
+
+def pack_kblob_gemm(blob):
+    """np_f16_pack_kblob_gemm: the weight records of a context with aero_gemm_order as a list-like ctypes float array (host only, no GPU)."""
+    lib = load()
+    lib.np_f16_pack_kblob_gemm.restype = C.c_int64
+    lib.np_f16_pack_kblob_gemm.argtypes = [C.c_char_p, C.c_size_t, C.c_void_p, C.c_int64]
+    n = lib.np_f16_pack_kblob_gemm(blob, len(blob), None, 0)
+    if n < 0:
+        check(1)
+    out = (C.c_float * n)()
+    if lib.np_f16_pack_kblob_gemm(blob, len(blob), out, n) != n:
+        check(1)
+    return out
 
 
 EXPORTS = ('np_abi_version', 'np_f16_airframe_default', 'np_f16_cache_floats', 'np_last_error', 'np_f16_ctx_create', 'np_f16_ctx_destroy', 'np_f16_reset',
            'np_f16_step', 'np_f16_derived', 'np_f16_aero_coefficients', 'np_f16_lowlevel_obs', 'np_f16_set_timing', 'np_f16_get_timing', 'np_f16_get_timing_samples', 'np_f16_set_trace', 'np_selfcheck_divc',
-           'np_f16_combat_ctx_create', 'np_f16_combat_reset', 'np_f16_combat_step', 'np_f16_set_kernel_variant', 'np_actor_forward', 'np_rollout_returns', 'np_planning_inner_loop', 'np_planning_check', 'np_actor_pack_i8', 'np_rollout_insert', 'np_policy_act', 'np_planning_targets_obs', 'np_dispatch_plan')
+           'np_f16_combat_ctx_create', 'np_f16_combat_reset', 'np_f16_combat_step', 'np_f16_set_kernel_variant', 'np_actor_forward', 'np_rollout_returns', 'np_planning_inner_loop', 'np_planning_check', 'np_actor_pack_i8', 'np_rollout_insert', 'np_policy_act', 'np_planning_targets_obs', 'np_dispatch_plan', 'np_dispatch_plan_gemm', 'np_f16_pack_kblob_gemm')
 KERNEL_VARIANTS = {'auto': 0, 'latency': 1, 'throughput': 2, 'pair': 3, 'latency8': 4, 'latency2': 5, 'latency4w': 6, 'dual8': 7, 'dual4': 8}
 
 _lib = None

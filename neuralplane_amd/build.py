@@ -15,6 +15,7 @@ SO = os.path.join(CSRC, 'libneuralplane_hip.so')
 # one translation unit per task x solver for the env.step / env.reset kernels (np_env_tu.inc): the six compile side by side (the rk4 units
 # are the long ones: ~2 min each), beside the host side + SingleCombat / controller kernels, the persistent PlanningEnv kernel and the dual family
 SOURCES = ['np_env_t0s1.hip', 'np_env_t1s1.hip', 'np_env_t2s1.hip', 'np_env_t0s0.hip', 'np_env_t1s0.hip', 'np_env_t2s0.hip',
+           'np_env_gemm_t0s1.hip', 'np_env_gemm_t1s1.hip', 'np_env_gemm_t2s1.hip', 'np_env_gemm_t0s0.hip', 'np_env_gemm_t1s0.hip', 'np_env_gemm_t2s0.hip',
            'np_f16_kernels.hip', 'np_planning.hip', 'np_combat_lat.hip', 'np_actor_i8.hip', 'np_policy.hip']
 HEADERS = ['np_f16_device.h', 'np_f16_kargs.h', 'np_f16_env_kernel.h', 'np_env_launch.h', 'np_env_tu.inc', 'np_planning.h', 'np_dispatch.h', 'np_f16_combat.h', 'np_actor.h', 'np_actor_i8.h', 'np_rollout.h', 'np_policy.h', 'np_actor_asm.inc', 'np_actor_mfma_asm.inc', 'np_actor_mfma16_asm.inc', 'np_math.h', 'np_nets.h', 'np_mlp_asm.inc', 'np_mlp_asm_dual.inc', os.path.join('..', '..', 'include', 'neuralplane_amd.h')]
 # -disable-machine-licm: the SingleCombat kernel's inner loop (5 FDM steps) otherwise gets ~40 loop-invariant 64-bit constants of the
@@ -22,6 +23,18 @@ HEADERS = ['np_f16_device.h', 'np_f16_kargs.h', 'np_f16_env_kernel.h', 'np_env_l
 # re-materialised inside the loop it needs 200 and no scratch (the other kernels have no loops and compile identically)
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-ffp-contract=off', '-fno-fast-math', '-fPIC', '-mllvm', '-disable-machine-licm']
 OBJ_DIR = os.path.join(CSRC, 'build')
+# np_mlp_asm_gemm.inc (the GEMM-order bodies of the numerics option aero_gemm_order) is generated here, not committed: 0.9 MB of text that
+# tools/gen_mlp_asm.py writes deterministically (tests/test_gemm_order_cpu.py); git-ignored, it sits beside the committed .inc files
+GENERATOR = os.path.join(os.path.dirname(HERE), 'tools', 'gen_mlp_asm.py')
+GEMM_INC = os.path.join(CSRC, 'np_mlp_asm_gemm.inc')
+
+
+def generate_gemm_inc():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location('_np_gen_mlp_asm', GENERATOR)
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    return gen.gen_gemm_file(CSRC)
 
 
 def _hipcc():
@@ -32,11 +45,11 @@ def _hipcc():
 
 
 def _deps():
-    return [os.path.join(CSRC, f) for f in HEADERS] + [os.path.abspath(__file__)]
+    return [os.path.join(CSRC, f) for f in HEADERS] + [os.path.abspath(__file__), GENERATOR]
 
 
 def is_stale():
-    if not os.path.exists(SO):
+    if not os.path.exists(SO) or not os.path.exists(GEMM_INC):
         return True
     t = os.path.getmtime(SO)
     return any(os.path.getmtime(d) > t for d in _deps() + [os.path.join(CSRC, f) for f in SOURCES])
@@ -49,6 +62,7 @@ def build_hip(force=False, verbose=False):
         return SO
     extra = os.environ.get('NPF16_EXTRA_FLAGS', '').split()  # tuning experiments only (e.g. -DNPF16_BLOCK=64)
     os.makedirs(OBJ_DIR, exist_ok=True)
+    generate_gemm_inc()
     stamp = os.path.join(OBJ_DIR, 'flags.txt')
     flags_now = ' '.join(FLAGS + extra)
     same_flags = os.path.exists(stamp) and open(stamp).read() == flags_now

@@ -24,7 +24,7 @@ NUM_NETS = 43
 NUM_CACHED = 14
 
 
-def cfg_from_config(config, task, solver=None, aero_1d_tables=None):
+def cfg_from_config(config, task, solver=None, aero_1d_tables=None, aero_gemm_order=None):
     """Scenario attribute bag (parse_config) -> np_f16_cfg, with the reference's getattr defaults."""
     g = lambda k, d: getattr(config, k, d)  # noqa: E731
     c = _lib.NpF16Cfg()
@@ -55,6 +55,11 @@ def cfg_from_config(config, task, solver=None, aero_1d_tables=None):
     if aero_1d_tables is None:
         aero_1d_tables = g('aero_1d_tables', int(os.environ.get('NPF16_AERO_1D_TABLES', '0')))
     c.aero_1d_tables = 1 if aero_1d_tables else 0
+    # numerics option aero_gemm_order (the aero MLPs' Linear layers as dot product + bias, the reference's nn.Linear order):
+    # keyword, else scenario key `aero_gemm_order`, else env NPF16_AERO_GEMM_ORDER, else off
+    if aero_gemm_order is None:
+        aero_gemm_order = g('aero_gemm_order', int(os.environ.get('NPF16_AERO_GEMM_ORDER', '0')))
+    c.aero_gemm_order = 1 if aero_gemm_order else 0
     # the airframe as data (not a reference key: the reference spells these as literals, F16_dynamics.py:61-76): scenario key `airframe`, a
     # mapping of np_f16_airframe fields that differ from the F-16's, e.g. {mass: 700, Jy: 60000}; absent / empty = the F-16
     c.airframe = _lib.airframe(g('airframe', None))
@@ -70,6 +75,13 @@ def _check_numerics_spec(sd):
                       'trajectories will differ in the last bits from a run recorded under the old spec', RuntimeWarning, stacklevel=3)
 
 
+def _check_gemm_order(sd, gemm_order):
+    if bool(sd.get('aero_gemm_order', False)) != bool(gemm_order):
+        import warnings
+        warnings.warn(f"checkpoint written with aero_gemm_order={bool(sd.get('aero_gemm_order', False))}, this context has aero_gemm_order={bool(gemm_order)}: "
+                      'the state loads, but the continued trajectories will differ in the last bits from the run that wrote it', RuntimeWarning, stacklevel=3)
+
+
 def _check_airframe(sd, airframe):
     """A checkpoint written with another np_f16_airframe block would continue on a different aircraft: refuse it (checkpoints from before
     round 6 carry no block: they were the F-16, i.e. the all-zero block)."""
@@ -83,7 +95,7 @@ def _check_airframe(sd, airframe):
 class F16Batch:
     """N aircraft on one GPU.  `row0` is the global index of local row 0 (sharded batches)."""
 
-    def __init__(self, n, config, task, device, seed=0, solver=None, row0=0, blob_path=ASSET_BLOB, aero_1d_tables=None):
+    def __init__(self, n, config, task, device, seed=0, solver=None, row0=0, blob_path=ASSET_BLOB, aero_1d_tables=None, aero_gemm_order=None):
         self.lib = _lib.load()
         self.device = torch.device(device)
         if self.device.type != 'cuda':
@@ -93,8 +105,9 @@ class F16Batch:
             self.device = torch.device('cuda', torch.cuda.current_device())
         self.n = int(n)
         self.task = task
-        self.cfg = cfg_from_config(config, task, solver, aero_1d_tables)
+        self.cfg = cfg_from_config(config, task, solver, aero_1d_tables, aero_gemm_order)
         self.aero_1d_tables = bool(self.cfg.aero_1d_tables)
+        self.aero_gemm_order = bool(self.cfg.aero_gemm_order)
         self.noise_scale = float(self.cfg.noise_scale)
         self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         self.row0 = int(row0)
@@ -422,12 +435,14 @@ class F16Batch:
         return {'s': self.s.clone(), 'u': self.u.clone(), 'tgt': self.tgt.clone(), 'step_count': self.step_count.clone(),
                 'flags': self.flags.clone(), 'call_idx': int(self.call_idx), 'seed': int(self.seed), 'row0': int(self.row0),
                 'task': self.task, 'n': self.n, 'numerics_spec': NUMERICS_SPEC, 'abi_version': _lib.ABI_VERSION,
+                'aero_gemm_order': self.aero_gemm_order,
                 'airframe': bytes(self.cfg.airframe)}   # np_f16_airframe as built (all zero = the F-16): a resumed run must fly the same aircraft
 
     def load_state_dict(self, sd):
         if sd['n'] != self.n or sd['task'] != self.task:
             raise ValueError(f"checkpoint is for n={sd['n']}, task={sd['task']}; this batch is n={self.n}, task={self.task}")
         _check_numerics_spec(sd)
+        _check_gemm_order(sd, self.aero_gemm_order)
         _check_airframe(sd, self.cfg.airframe)
         for k in ('s', 'u', 'tgt', 'step_count'):
             getattr(self, k).copy_(sd[k].to(self.device))
@@ -500,7 +515,7 @@ NUM_PID = 11
 NUM_OBS_COMBAT = 15
 
 
-def combat_cfg_from_config(config, solver=None, aero_1d_tables=None, pid_dir=PID_CONFIG_DIR):
+def combat_cfg_from_config(config, solver=None, aero_1d_tables=None, pid_dir=PID_CONFIG_DIR, aero_gemm_order=None):
     """selfplay attribute bag + pid/*.yaml -> np_f16_combat_cfg (defaults: singlecombat_env.py:29-44, the condition classes)."""
     import yaml
     g = lambda k, d: getattr(config, k, d)  # noqa: E731
@@ -539,6 +554,11 @@ def combat_cfg_from_config(config, solver=None, aero_1d_tables=None, pid_dir=PID
     if aero_1d_tables is None:
         aero_1d_tables = g('aero_1d_tables', int(os.environ.get('NPF16_AERO_1D_TABLES', '0')))
     c.aero_1d_tables = 1 if aero_1d_tables else 0
+    # aero_gemm_order: keyword or scenario key only — SingleCombat has no GEMM-order kernels and np_f16_combat_ctx_create refuses the option, so
+    # the process-wide NPF16_AERO_GEMM_ORDER (a switch for measuring the env kernels) does not reach this cfg
+    if aero_gemm_order is None:
+        aero_gemm_order = g('aero_gemm_order', 0)
+    c.aero_gemm_order = 1 if aero_gemm_order else 0
     return c
 
 
@@ -546,7 +566,7 @@ class F16CombatBatch:
     """num_envs 1v1 engagements (2*num_envs aircraft, rows 2k / 2k+1 = ego / enemy of env k) on one GPU.
     `env0` is the global index of local env 0 (sharded batches: partition by env, never by aircraft)."""
 
-    def __init__(self, num_envs, config, device, seed=0, solver=None, env0=0, blob_path=ASSET_BLOB, aero_1d_tables=None):
+    def __init__(self, num_envs, config, device, seed=0, solver=None, env0=0, blob_path=ASSET_BLOB, aero_1d_tables=None, aero_gemm_order=None):
         self.lib = _lib.load()
         self.device = torch.device(device)
         if self.device.type != 'cuda':
@@ -556,7 +576,9 @@ class F16CombatBatch:
             self.device = torch.device('cuda', torch.cuda.current_device())
         self.num_envs = int(num_envs)
         self.n = 2 * self.num_envs
-        self.cfg = combat_cfg_from_config(config, solver, aero_1d_tables)
+        self.cfg = combat_cfg_from_config(config, solver, aero_1d_tables, aero_gemm_order=aero_gemm_order)
+        if self.cfg.aero_gemm_order:
+            raise ValueError('aero_gemm_order: SingleCombat has no GEMM-order kernels (two-set bodies only); leave the option off')
         self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         self.env0 = int(env0)
         self.call_idx = 0

@@ -67,11 +67,13 @@ constexpr int LAT_TILE = 64;
 // step: np_f16_step (false: np_f16_reset); solver 0 Euler / 1 rk4; tables: the 1-D table numerics; variant: the context's pin (K_AUTO = none);
 // env_kernel: NPF16_KERNEL as a variant number (K_AUTO = unset; latency, throughput or pair); pair_waves_env: NPF16_PAIR_WAVES (0 = unset);
 // block: NPF16_BLOCK (128)
-inline EnvChoice env_choice(int64_t n, int cus, bool step, int solver, bool tables, int variant, int env_kernel, int pair_waves_env, int block) {
+// gemm: the context's aero_gemm_order — single-set kernels only, so never the pair family (large batches take the throughput variant)
+inline EnvChoice env_choice(int64_t n, int cus, bool step, int solver, bool tables, int variant, int env_kernel, int pair_waves_env, int block,
+                            bool gemm = false) {
     const Limits l = limits_for(cus);
     EnvChoice c = {};
     const bool pair_auto = env_kernel == K_PAIR || (env_kernel == K_AUTO && n > l.lat_max_n);
-    c.pair = step && (variant != K_AUTO ? variant == K_PAIR : pair_auto);
+    c.pair = !gemm && step && (variant != K_AUTO ? variant == K_PAIR : pair_auto);
     const int v = variant != K_AUTO ? variant : (env_kernel == K_LATENCY || env_kernel == K_THROUGHPUT) ? env_kernel : K_AUTO;
     const bool lat_family = v != K_AUTO ? (v == K_LATENCY || v == K_LATENCY8 || v == K_LATENCY2 || v == K_LATENCY4W) : n <= l.lat_max_n;
     c.latency = !c.pair && step && solver == 0 && lat_family;

@@ -27,5 +27,12 @@ void env_dispatch_t1s0(const EnvLaunch &l);
 void env_dispatch_t1s1(const EnvLaunch &l);
 void env_dispatch_t2s0(const EnvLaunch &l);
 void env_dispatch_t2s1(const EnvLaunch &l);
+// the same six for contexts with aero_gemm_order (np_env_gemm_t{task}s{solver}.hip): f16_env_kernel_gemm, single-set family only
+void env_dispatch_gemm_t0s0(const EnvLaunch &l);
+void env_dispatch_gemm_t0s1(const EnvLaunch &l);
+void env_dispatch_gemm_t1s0(const EnvLaunch &l);
+void env_dispatch_gemm_t1s1(const EnvLaunch &l);
+void env_dispatch_gemm_t2s0(const EnvLaunch &l);
+void env_dispatch_gemm_t2s1(const EnvLaunch &l);
 
 }  // namespace npf16

@@ -26,6 +26,7 @@ struct AeroWeights {
     const float *kblob_dual;  // [KBLOB_DUAL_FLOATS] the same nets in the record layout of the two-set bodies (np_nets.h)
     const float *pwl;         // [NUM_PWL_TABLES * PWL_TABLE_FLOATS] or null
     const float *pwl_unnorm;  // [NUM_PWL_TABLES * 2] or null
+    const float *kblob_gemm;  // [KBLOB_GEMM_FLOATS] the records of the GEMM-order bodies (np_nets.h), or null: contexts with aero_gemm_order only
 };
 
 // The airframe as data (np_f16_airframe, ABI 16): what F16Dynamics.nlplant / atmos and F16Model.update spell as literals
@@ -187,6 +188,7 @@ __device__ __forceinline__ float mlp_body(const float *kblob, int w, const float
 #endif
 #include "np_mlp_asm.inc"
 #include "np_mlp_asm_dual.inc"
+#include "np_mlp_asm_gemm.inc"
 
 // All nets of one class (np_nets.h): same shape, same inputs, KBLOB records back to back.  ONE
 // compact loop body per class keeps the instruction footprint of a full aero evaluation at a few
@@ -228,11 +230,22 @@ __device__ __forceinline__ void eval_class_pwl(const AeroWeights &wt, float x, f
     }
 }
 
-template <int CL, int COUNT, int LD, int FIRST = 0>  // nets [FIRST, FIRST+COUNT) of class CL
+// GEMM (numerics option aero_gemm_order, compile time): the GEMM-order bodies on wt.kblob_gemm — no table mode, no C++ twin
+template <int CL, int COUNT, int LD, int FIRST = 0, bool GEMM = false>  // nets [FIRST, FIRST+COUNT) of class CL
 __device__ __forceinline__ void eval_class(const AeroWeights &wt, const float (&xn)[NUM_NORM_GROUPS], float *__restrict__ out, bool tables) {
     constexpr NetClass c = CLASSES[CL];
     constexpr int n = COUNT;
     static_assert(COUNT >= 0 && FIRST >= 0 && FIRST + COUNT <= c.count, "class range");
+    if constexpr (GEMM) {
+        if constexpr (n > 0) {
+            const unsigned lds_addr = (unsigned)(unsigned long long)(out + (class_slot(CL) + FIRST) * LD);
+            const float x0 = xn[c.grp[0]];
+            const float x1 = c.n_in > 1 ? xn[c.grp[c.n_in > 1 ? 1 : 0]] : 0.0f;
+            const float x2 = c.n_in > 2 ? xn[c.grp[c.n_in > 2 ? 2 : 0]] : 0.0f;
+            mlp_class_asm_gemm<c.n_in, c.h1, c.h2, c.h3, n, (int)(LD * sizeof(float))>(wt.kblob_gemm + gemm_class_base(CL) + FIRST * gemm_class_stride(CL), lds_addr, x0, x1, x2);
+        }
+        return;
+    }
     if constexpr (c.n_in == 1 && n > 0) {
         if (tables) {  // wave-uniform
             eval_class_pwl<CL, COUNT, LD, FIRST>(wt, xn[c.grp[0]], out);
@@ -278,11 +291,11 @@ __device__ __forceinline__ void eval_class(const AeroWeights &wt, const float (&
 // the force-side evaluation extended to all 36 (what the NEXT integrator evaluation will find there) — the 22 moment-side nets move from
 // the front of an inner step, which the controller's next call waits for, to its back, which runs beside that call.
 enum AbPart : int { AB_ALL = 0, AB_FORCE = 1, AB_REST = 2, AB_EL = 3, AB_ABALL = 4, AB_GRU = 5 };
-template <int LD, int PART>
+template <int LD, int PART, bool GEMM = false>
 __device__ __forceinline__ void eval_ab(const AeroWeights &wt, const float (&xn)[NUM_NORM_GROUPS], float *__restrict__ out, bool tables) {
 #define NPF16_CLS(cl)                                                                                      \
     eval_class<cl, (PART == AB_ALL ? CLASSES[cl].count : PART == AB_FORCE ? CLASSES[cl].n_force : CLASSES[cl].count - CLASSES[cl].n_force), \
-               LD, (PART == AB_REST ? CLASSES[cl].n_force : 0)>(wt, xn, out, tables)
+               LD, (PART == AB_REST ? CLASSES[cl].n_force : 0), GEMM>(wt, xn, out, tables)
     NPF16_CLS(CL_DAMP);
     NPF16_CLS(CL_DLEF);
     NPF16_CLS(CL_D_RUD);
@@ -295,10 +308,10 @@ __device__ __forceinline__ void eval_ab(const AeroWeights &wt, const float (&xn)
 #undef NPF16_CLS
 }
 // the el-dependent nets: the first N_C of (Cx Cz Cm Cn Cl) and eta_el -> slots 36..41
-template <int N_C, int N_ETA, int LD>
+template <int N_C, int N_ETA, int LD, bool GEMM = false>
 __device__ __forceinline__ void eval_el(const AeroWeights &wt, const float (&xn)[NUM_NORM_GROUPS], float *__restrict__ out, bool tables) {
-    eval_class<CL_C, N_C, LD>(wt, xn, out, tables);
-    eval_class<CL_ETA, N_ETA, LD>(wt, xn, out, tables);
+    eval_class<CL_C, N_C, LD, 0, GEMM>(wt, xn, out, tables);
+    eval_class<CL_ETA, N_ETA, LD, 0, GEMM>(wt, xn, out, tables);
 }
 
 // ---- latency variant: the nets of one evaluation split over the 4 waves of a workgroup that share ONE tile of 64
@@ -449,10 +462,10 @@ static_assert(plan_covers(PLAN8_REST, AB_REST, 5, 1) && plan_covers(PLAN8_ALL, A
               "eight-wave split plans must cover each net of their phase exactly once");
 static_assert(plan_covers(PLAN8_EL, AB_EL, 5, 1) && plan_covers(PLAN_ABALL2, AB_ABALL, 2, 0), "the pipelined schedule's plans must cover each net of their phase exactly once");
 
-template <const SplitPlan &P, int W, int LD>
+template <const SplitPlan &P, int W, int LD, bool GEMM = false>
 __device__ __forceinline__ void eval_plan_wave(const AeroWeights &wt, const float (&xn)[NUM_NORM_GROUPS], float *__restrict__ out, bool tables) {
 #define NPF16_ITEM(K)                                                                                         \
-    if constexpr (P.it[W][K].cnt > 0) eval_class<P.it[W][K].cl, P.it[W][K].cnt, LD, P.it[W][K].first>(wt, xn, out, tables)
+    if constexpr (P.it[W][K].cnt > 0) eval_class<P.it[W][K].cl, P.it[W][K].cnt, LD, P.it[W][K].first, GEMM>(wt, xn, out, tables)
     NPF16_ITEM(0);
     NPF16_ITEM(1);
     NPF16_ITEM(2);
@@ -557,10 +570,10 @@ __device__ __forceinline__ void eval_plan_wave_dual(const AeroWeights &wt, const
 }
 
 // the same plans with ONE accumulator set (WPT_LAT2: the two waves hold the same 64 aircraft)
-template <const PairPlan &P, int W, int LD>
+template <const PairPlan &P, int W, int LD, bool GEMM = false>
 __device__ __forceinline__ void eval_pairplan_single(const AeroWeights &wt, const float (&xn)[NUM_NORM_GROUPS], float *__restrict__ out, bool tables) {
 #define NPF16_ITEM(K) \
-    if constexpr (P.it[W][K].cnt > 0) eval_class<P.it[W][K].cl, P.it[W][K].cnt, LD, P.it[W][K].first>(wt, xn, out, tables)
+    if constexpr (P.it[W][K].cnt > 0) eval_class<P.it[W][K].cl, P.it[W][K].cnt, LD, P.it[W][K].first, GEMM>(wt, xn, out, tables)
     NPF16_ITEM(0);
     NPF16_ITEM(1);
     NPF16_ITEM(2);
@@ -577,9 +590,10 @@ __device__ __forceinline__ void eval_pairplan_single(const AeroWeights &wt, cons
 #ifndef NPF16_PHASE_ASM
 #define NPF16_PHASE_ASM 1
 #endif
-template <int LD, int PART, bool FULL, int WPT = 1>
+template <int LD, int PART, bool FULL, int WPT = 1, bool GEMM = false>
 __device__ __forceinline__ void eval_nets(const AeroWeights &wt, const float (&xn)[NUM_NORM_GROUPS], float *__restrict__ out, bool tables, int part = 0) {
     constexpr bool has_phase = (FULL && (PART == AB_ALL || PART == AB_REST)) || (!FULL && PART == AB_FORCE);
+    static_assert(!GEMM || (WPT != 2 && dual_waves(WPT) == 0), "aero_gemm_order has single-set bodies only: no pair / dual family");
     static_assert((PART != AB_EL && PART != AB_ABALL && PART != AB_GRU) || (PART == AB_EL && FULL && WPT == 8) || ((PART == AB_ABALL || PART == AB_GRU) && !FULL && WPT == 4),
                   "AB_EL / AB_ABALL / AB_GRU exist as the eight-wave integrator plan and the four-wave force-side plans only");
     if constexpr (WPT == 2) {  // pair variant: `part` = this wave's index in its 128-aircraft workgroup
@@ -634,9 +648,9 @@ __device__ __forceinline__ void eval_nets(const AeroWeights &wt, const float (&x
         static_assert(has_phase, "no split plan for this evaluation");
         __syncthreads();  // both waves have finished reading the coefficients of the previous evaluation
 #define NPF16_WAVE(W)                                                                                        \
-    if constexpr (FULL && PART == AB_ALL) eval_pairplan_single<PAIR_ALL, W, LD>(wt, xn, out, tables);        \
-    else if constexpr (FULL && PART == AB_REST) eval_pairplan_single<PAIR_REST, W, LD>(wt, xn, out, tables); \
-    else eval_pairplan_single<PAIR_FORCE2, W, LD>(wt, xn, out, tables)
+    if constexpr (FULL && PART == AB_ALL) eval_pairplan_single<PAIR_ALL, W, LD, GEMM>(wt, xn, out, tables);        \
+    else if constexpr (FULL && PART == AB_REST) eval_pairplan_single<PAIR_REST, W, LD, GEMM>(wt, xn, out, tables); \
+    else eval_pairplan_single<PAIR_FORCE2, W, LD, GEMM>(wt, xn, out, tables)
         if (part == 0) { NPF16_WAVE(0); }
         else { NPF16_WAVE(1); }
 #undef NPF16_WAVE
@@ -682,19 +696,19 @@ __device__ __forceinline__ void eval_nets(const AeroWeights &wt, const float (&x
         __syncthreads();  // every wave has finished reading the coefficients of the previous evaluation
 #define NPF16_WAVE(W)                                                                                                    \
     if constexpr (PART == AB_EL) {                                                                                       \
-        eval_plan_wave<PLAN8_EL, W, LD>(wt, xn, out, tables);                                                            \
+        eval_plan_wave<PLAN8_EL, W, LD, GEMM>(wt, xn, out, tables);                                                            \
     } else if constexpr (PART == AB_ABALL) {                                                                             \
-        eval_plan_wave<PLAN_ABALL2, W, LD>(wt, xn, out, tables);                                                         \
+        eval_plan_wave<PLAN_ABALL2, W, LD, GEMM>(wt, xn, out, tables);                                                         \
     } else if constexpr (PART == AB_GRU) {                                                                               \
-        eval_plan_wave<PLAN_ABGRU, W, LD>(wt, xn, out, tables);                                                          \
+        eval_plan_wave<PLAN_ABGRU, W, LD, GEMM>(wt, xn, out, tables);                                                          \
     } else if constexpr (WPT == 8) {                                                                                     \
-        if constexpr (FULL && PART == AB_ALL) eval_plan_wave<PLAN8_ALL, W, LD>(wt, xn, out, tables);                     \
-        else if constexpr (FULL && PART == AB_REST) eval_plan_wave<PLAN8_REST, W, LD>(wt, xn, out, tables);              \
-        else eval_plan_wave<PLAN8_FORCE2, W, LD>(wt, xn, out, tables);                                                   \
+        if constexpr (FULL && PART == AB_ALL) eval_plan_wave<PLAN8_ALL, W, LD, GEMM>(wt, xn, out, tables);                     \
+        else if constexpr (FULL && PART == AB_REST) eval_plan_wave<PLAN8_REST, W, LD, GEMM>(wt, xn, out, tables);              \
+        else eval_plan_wave<PLAN8_FORCE2, W, LD, GEMM>(wt, xn, out, tables);                                                   \
     } else {                                                                                                             \
-        if constexpr (FULL && PART == AB_ALL) eval_plan_wave<PLAN_ALL, W, LD>(wt, xn, out, tables);                      \
-        else if constexpr (FULL && PART == AB_REST) eval_plan_wave<PLAN_REST, W, LD>(wt, xn, out, tables);               \
-        else eval_plan_wave<PLAN_FORCE2, W, LD>(wt, xn, out, tables);                                                    \
+        if constexpr (FULL && PART == AB_ALL) eval_plan_wave<PLAN_ALL, W, LD, GEMM>(wt, xn, out, tables);                      \
+        else if constexpr (FULL && PART == AB_REST) eval_plan_wave<PLAN_REST, W, LD, GEMM>(wt, xn, out, tables);               \
+        else eval_plan_wave<PLAN_FORCE2, W, LD, GEMM>(wt, xn, out, tables);                                                    \
     }
         if (part == 0) { NPF16_WAVE(0); }
         else if (part == 1) { NPF16_WAVE(1); }
@@ -711,6 +725,13 @@ __device__ __forceinline__ void eval_nets(const AeroWeights &wt, const float (&x
         return;
     } else {
 #if NPF16_ASM_MLP && NPF16_PHASE_ASM && !defined(NPF16_EXP)
+        if constexpr (has_phase && GEMM) {
+            const unsigned lds_base = (unsigned)(unsigned long long)out;
+            if constexpr (FULL && PART == AB_ALL) mlp_phase_asm_gemm_ALL<(int)(LD * sizeof(float))>(wt.kblob_gemm + MLP_PHASE_GEMM_ALL_START, lds_base, xn);
+            else if constexpr (FULL && PART == AB_REST) mlp_phase_asm_gemm_REST<(int)(LD * sizeof(float))>(wt.kblob_gemm + MLP_PHASE_GEMM_REST_START, lds_base, xn);
+            else mlp_phase_asm_gemm_FORCE2<(int)(LD * sizeof(float))>(wt.kblob_gemm + MLP_PHASE_GEMM_FORCE2_START, lds_base, xn);
+            return;
+        }
         if constexpr (has_phase) {
             if (!tables) {  // wave-uniform
                 const unsigned lds_base = (unsigned)(unsigned long long)out;
@@ -729,8 +750,8 @@ __device__ __forceinline__ void eval_nets(const AeroWeights &wt, const float (&x
             }
         }
 #endif
-        eval_ab<LD, PART>(wt, xn, out, tables);
-        eval_el<(FULL ? 5 : 2), (FULL ? 1 : 0), LD>(wt, xn, out, tables);
+        eval_ab<LD, PART, GEMM>(wt, xn, out, tables);
+        eval_el<(FULL ? 5 : 2), (FULL ? 1 : 0), LD, GEMM>(wt, xn, out, tables);
     }
 }
 
@@ -782,7 +803,8 @@ constexpr int NUM_SHARED_SCALARS = 12;
 // serial chains -> LDS and nothing else (no barrier: the caller publishes them); 2 = everything BUT the share computation (the set is
 // already in LDS and published).
 // AF: how the airframe constants are reached — AirframeVia<AP> (step kernels: re-read from the kernel arguments after the MLP phase) or Airframe
-template <bool FULL, int PART, int LD, int WPT = 1, bool SHARE = false, int SET = 0, bool HAVE_POW = false, int STAGE = 0, class AF>
+// GEMM: numerics option aero_gemm_order (the nets in GEMM order, eval_class)
+template <bool FULL, int PART, int LD, int WPT = 1, bool SHARE = false, int SET = 0, bool HAVE_POW = false, int STAGE = 0, bool GEMM = false, class AF>
 __device__ __forceinline__ void nlplant(const AeroWeights &wt, const AF &afv, const float (&s)[12], const float (&u)[4], StateScalars &sc,
                                         float *__restrict__ coef, bool tables, float (&xd)[12], int part = 0) {
     static_assert(!SHARE || WPT == 4 || WPT == 8 || WPT == WPT_LAT2, "shared state scalars belong to the latency variants");
@@ -866,7 +888,7 @@ __device__ __forceinline__ void nlplant(const AeroWeights &wt, const AF &afv, co
     const float chk = ((alpha - alpha) + (beta - beta)) + (el - el);
     const bool ok = (chk == chk);
     const float qnan = __builtin_nanf("");
-    eval_nets<LD, PART, FULL, WPT>(wt, xn, coef, tables, part);
+    eval_nets<LD, PART, FULL, WPT, GEMM>(wt, xn, coef, tables, part);
     // "non-finite inputs poison every coefficient": every coefficient enters xdot through one of the six totals below, and a NaN
     // coefficient makes its total NaN — so the rule is applied to the six totals (six selects) instead of to each of the 42 / 16
     // coefficient reads; same values, same NaN-ness of every output (the payload of a NaN is not part of the spec)
@@ -967,7 +989,7 @@ __device__ __forceinline__ void nlplant(const AeroWeights &wt, const AF &afv, co
 }
 
 // the state's trigonometry computed by the caller (every variant but the latency one)
-template <bool FULL, int PART, int LD, int WPT = 1, class AF>
+template <bool FULL, int PART, int LD, int WPT = 1, bool GEMM = false, class AF>
 __device__ __forceinline__ void nlplant(const AeroWeights &wt, const AF &afv, const float (&s)[12], const float (&u)[4], const Trig &tr, float tt, float spsi,
                                         float cpsi, float *__restrict__ coef, bool tables, float (&xd)[12], int part = 0) {
     StateScalars sc;
@@ -975,7 +997,7 @@ __device__ __forceinline__ void nlplant(const AeroWeights &wt, const AF &afv, co
     sc.tt = tt;
     sc.spsi = spsi;
     sc.cpsi = cpsi;
-    nlplant<FULL, PART, LD, WPT, false, 0>(wt, afv, s, u, sc, coef, tables, xd, part);
+    nlplant<FULL, PART, LD, WPT, false, 0, false, 0, GEMM>(wt, afv, s, u, sc, coef, tables, xd, part);
 }
 
 // F16Model.update's first-order control lag (F16_model.py:52-62), left to right exactly as written:
@@ -996,14 +1018,14 @@ __device__ __forceinline__ void trig_of(const float (&s)[12], Trig &tr, float &t
 }
 
 // full derivative at (s,u) including the heading terms
-template <int PART, int LD, int WPT = 1, class AF>
+template <int PART, int LD, int WPT = 1, bool GEMM = false, class AF>
 __device__ __forceinline__ void xdot_full(const AeroWeights &wt, const AF &afv, const float (&s)[12], const float (&u)[4], float *__restrict__ coef, bool tables,
                                           float (&xd)[12], int part = 0) {
     Trig tr;
     float tt, spsi, cpsi;
     trig_of(s, tr, tt);
     np_sincos(s[5], spsi, cpsi);
-    nlplant<true, PART, LD, WPT>(wt, afv, s, u, tr, tt, spsi, cpsi, coef, tables, xd, part);
+    nlplant<true, PART, LD, WPT, GEMM>(wt, afv, s, u, tr, tt, spsi, cpsi, coef, tables, xd, part);
 }
 // F16Model.get_acceleration — F16_model.py:132-148, from xdot[6..8] at (s,u)
 __device__ __forceinline__ void body_acceleration(const float (&s)[12], const Trig &tr, const float (&xd)[12], float (&a)[3]) {

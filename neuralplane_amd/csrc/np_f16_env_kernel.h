@@ -1,7 +1,14 @@
 // np_f16_env_kernel.h — the fused F-16 env.step / env.reset kernel template (reference: envs/env_base.py:83-109), shared by the
 // translation units that instantiate it: np_env_t{0,1,2}s{0,1}.hip (one per task x solver, built in parallel; np_env_tu.inc) — the host
 // side (context, dispatch rule, C ABI) is np_f16_kernels.hip, which hands a launch over through np_env_launch.h.
-#pragma once
+// This header is included ONCE for f16_env_kernel and, in the units of the GEMM-order kernels (np_env_tu.inc with NP_ENV_GEMM), a SECOND time with
+// NP_ENV_KERNEL_NAME = f16_env_kernel_gemm and NP_ENV_KERNEL_GEMM = true: the same kernel text with the aero nets in GEMM order (numerics option
+// aero_gemm_order) as a kernel template of its own — never a run-time branch, and f16_env_kernel stays, token for token, the kernel it was.
+#ifndef NP_F16_ENV_KERNEL_H
+#define NP_F16_ENV_KERNEL_H
+#define NP_ENV_KERNEL_NAME f16_env_kernel
+#define NP_ENV_KERNEL_GEMM false
+#define NP_F16_ENV_KERNEL_FIRST_PASS
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
@@ -47,6 +54,12 @@ namespace npf16 {
 #ifndef NPF16_STAGGER_CYCLES_LONG
 #define NPF16_STAGGER_CYCLES_LONG 30000  // grids of 8 generations and more (N >= 1.6e6 on 256 CUs), see the kernel
 #endif
+#endif  // NP_F16_ENV_KERNEL_H (the preamble)
+#ifndef NP_F16_ENV_KERNEL_FIRST_PASS
+namespace npf16 {
+#endif
+#undef NP_F16_ENV_KERNEL_FIRST_PASS
+
 // STEP=true : BaseEnv.step  (env_base.py:99-109)
 // STEP=false: BaseEnv.reset (env_base.py:83-97)
 // CACHED    : a.cache holds, for every row, the 14 force-side alpha/beta-only coefficients of its CURRENT
@@ -66,7 +79,8 @@ template <int TASK, int SOLVER, bool STEP, bool CACHED, int TILE = BLOCK, int WP
 // grid sizes where six workgroups per CU are placed unevenly), latency4w four, everything else NPF16_MINWAVES
 __global__ __launch_bounds__(TILE * lat_waves(WPT))
 __attribute__((amdgpu_waves_per_eu((WPT == 2 ? PW : (WPT == 4 && PW == 4) ? 4 : NPF16_MINWAVES), (WPT == 2 && PW == 2 ? 2 : 8))))
-void f16_env_kernel(const KArgs a) {
+void NP_ENV_KERNEL_NAME(const KArgs a) {
+    constexpr bool GEMM = NP_ENV_KERNEL_GEMM;  // numerics option aero_gemm_order (np_f16_device.h::eval_class), a compile-time constant of this instantiation
     // latency variant with shared scalar work (Euler step): wave w computes a quarter of the tile's serial fp64 chains and of its
     // observation noise for ALL four waves (np_f16_device.h::nlplant<.., SHARE>), wave 0 finishes the observation, wave 1 the
     // terminations / reward / state stores
@@ -261,12 +275,12 @@ void f16_env_kernel(const KArgs a) {
                 float xd_[12];
                 if constexpr (SHARED) {
                     StateScalars scx;
-                    nlplant<false, AB_FORCE, TILE, WPT, true, 1>(a.wt, airframe_via(ap), s, u, scx, coef, tables, xd_, pw);
+                    nlplant<false, AB_FORCE, TILE, WPT, true, 1, false, 0, GEMM>(a.wt, airframe_via(ap), s, u, scx, coef, tables, xd_, pw);
                 } else {   // one wave on its own (the pair variant's two waves hold different rows and decide for themselves)
                     StateScalars scx;
                     trig_of(s, scx.tr, scx.tt);
                     scx.spsi = scx.cpsi = 0.0f;
-                    nlplant<false, AB_FORCE, TILE, 1, false, 0>(a.wt, airframe_via(ap), s, u, scx, coef, tables, xd_, 0);
+                    nlplant<false, AB_FORCE, TILE, 1, false, 0, false, 0, GEMM>(a.wt, airframe_via(ap), s, u, scx, coef, tables, xd_, 0);
                 }
 #endif
             }
@@ -319,14 +333,14 @@ void f16_env_kernel(const KArgs a) {
             NP_LT(1);
             if constexpr (SHARED) {
                 StateScalars sc0;
-                nlplant<true, (CACHED ? AB_REST : AB_ALL), TILE, WPT, true, 0>(a.wt, airframe_via(ap), s, u, sc0, coef, tables, k1, pw);
+                nlplant<true, (CACHED ? AB_REST : AB_ALL), TILE, WPT, true, 0, false, 0, GEMM>(a.wt, airframe_via(ap), s, u, sc0, coef, tables, k1, pw);
                 NP_LT(2);
             } else if constexpr (TRIG_CACHED) {  // the state's trigonometry comes from the cache; only the heading's is evaluated here
                 np_sincos(s[5], sc_old.spsi, sc_old.cpsi);
-                nlplant<true, AB_REST, TILE, WPT, false, 0, true>(a.wt, airframe_via(ap), s, u, sc_old, coef, tables, k1, pw);
+                nlplant<true, AB_REST, TILE, WPT, false, 0, true, 0, GEMM>(a.wt, airframe_via(ap), s, u, sc_old, coef, tables, k1, pw);
                 NP_LT(2);
             } else {
-                xdot_full<(CACHED ? AB_REST : AB_ALL), TILE, WPT>(a.wt, airframe_via(ap), s, u, coef, tables, k1, pw);
+                xdot_full<(CACHED ? AB_REST : AB_ALL), TILE, WPT, GEMM>(a.wt, airframe_via(ap), s, u, coef, tables, k1, pw);
                 NP_LT(2);
             }
             NP_REREAD_ARGS(ap);
@@ -345,10 +359,10 @@ void f16_env_kernel(const KArgs a) {
                 // weights pointer and numerics switch re-read per stage: nothing scalar but `ap` stays live across the asm phases (they
                 // own s4-s101; the statement's record pointer and `ap` fill s0-s3)
                 NP_REREAD_ARGS(ap);
-                const AeroWeights wts = {ap->wt.kblob, ap->wt.kblob_dual, ap->wt.pwl, ap->wt.pwl_unnorm};
+                const AeroWeights wts = {ap->wt.kblob, ap->wt.kblob_dual, ap->wt.pwl, ap->wt.pwl_unnorm, GEMM ? ap->wt.kblob_gemm : nullptr};
                 const bool tbs = ap->cfg.aero_1d_tables != 0;
-                if (CACHED && stage == 0) xdot_full<AB_REST, TILE, WPT>(wts, airframe_via(ap), y, u, coef, tbs, kk, pw);  // y == s: cached coefficients apply
-                else xdot_full<AB_ALL, TILE, WPT>(wts, airframe_via(ap), y, u, coef, tbs, kk, pw);
+                if (CACHED && stage == 0) xdot_full<AB_REST, TILE, WPT, GEMM>(wts, airframe_via(ap), y, u, coef, tbs, kk, pw);  // y == s: cached coefficients apply
+                else xdot_full<AB_ALL, TILE, WPT, GEMM>(wts, airframe_via(ap), y, u, coef, tbs, kk, pw);
                 if (stage == 0) {
 #pragma unroll
                     for (int k = 0; k < 12; k++) {
@@ -418,10 +432,10 @@ void f16_env_kernel(const KArgs a) {
         pow_new = atmos_pow(ap->cfg.af, s[2]);
 #else
         {
-            const AeroWeights wt2 = {ap->wt.kblob, ap->wt.kblob_dual, ap->wt.pwl, ap->wt.pwl_unnorm};
+            const AeroWeights wt2 = {ap->wt.kblob, ap->wt.kblob_dual, ap->wt.pwl, ap->wt.pwl_unnorm, GEMM ? ap->wt.kblob_gemm : nullptr};
             if constexpr (SHARED) {
                 NP_LT(3);
-                nlplant<false, AB_FORCE, TILE, WPT, true, 1>(wt2, airframe_via(ap), s, u, sc1, coef, ap->cfg.aero_1d_tables != 0, xd, pw);
+                nlplant<false, AB_FORCE, TILE, WPT, true, 1, false, 0, GEMM>(wt2, airframe_via(ap), s, u, sc1, coef, ap->cfg.aero_1d_tables != 0, xd, pw);
                 NP_LT(4);
                 tr = sc1.tr;
                 tt_new = sc1.tt;
@@ -431,7 +445,7 @@ void f16_env_kernel(const KArgs a) {
                 StateScalars scn;
                 scn.tr = tr;
                 scn.tt = scn.spsi = scn.cpsi = 0.0f;
-                nlplant<false, AB_FORCE, TILE, WPT, false, 0>(wt2, airframe_via(ap), s, u, scn, coef, ap->cfg.aero_1d_tables != 0, xd, pw);
+                nlplant<false, AB_FORCE, TILE, WPT, false, 0, false, 0, GEMM>(wt2, airframe_via(ap), s, u, scn, coef, ap->cfg.aero_1d_tables != 0, xd, pw);
                 pow_new = scn.powv;
                 NP_LT(4);
             }

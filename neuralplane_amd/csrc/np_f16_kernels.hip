@@ -43,9 +43,9 @@ namespace npf16 {
 
 
 // F16Model getters that need the dynamics or the atmosphere (F16_model.py:47-49, 132-198): out[23][ld_out]
-__global__ __launch_bounds__(BLOCK) void f16_derived_kernel(const float *__restrict__ sp, const float *__restrict__ up,
-                                                            long long ld, float *__restrict__ out, long long ld_out,
-                                                            long long n, float airspeed, int tables, AeroWeights wt, Airframe af) {
+template <bool GEMM>
+__device__ __forceinline__ void f16_derived_body(const float *__restrict__ sp, const float *__restrict__ up, long long ld, float *__restrict__ out,
+                                                 long long ld_out, long long n, float airspeed, int tables, const AeroWeights &wt, const Airframe &af) {
     __shared__ float lds[NUM_LDS_SLOTS * BLOCK];
     float *coef = lds + threadIdx.x;
     const long long i = (long long)blockIdx.x * BLOCK + threadIdx.x;
@@ -61,7 +61,7 @@ __global__ __launch_bounds__(BLOCK) void f16_derived_kernel(const float *__restr
     trig_of(s, tr, tt);
     np_sincos(s[5], spsi, cpsi);
     float xd[12];
-    nlplant<true, AB_ALL, BLOCK>(wt, af, s, u, tr, tt, spsi, cpsi, coef, tables != 0, xd);
+    nlplant<true, AB_ALL, BLOCK, 1, GEMM>(wt, af, s, u, tr, tt, spsi, cpsi, coef, tables != 0, xd);
     float a3[3];
     body_acceleration(s, tr, xd, a3);
     const float inv_grav = (float)(1.0 / 32.174), minv_grav = (float)(-1.0 / 32.174);  // F16_model.py:166,176-178
@@ -93,14 +93,25 @@ __global__ __launch_bounds__(BLOCK) void f16_derived_kernel(const float *__restr
     out[21 * ld_out + i] = qbar;
     out[22 * ld_out + i] = ps;
 }
+__global__ __launch_bounds__(BLOCK) void f16_derived_kernel(const float *__restrict__ sp, const float *__restrict__ up,
+                                                            long long ld, float *__restrict__ out, long long ld_out,
+                                                            long long n, float airspeed, int tables, AeroWeights wt, Airframe af) {
+    f16_derived_body<false>(sp, up, ld, out, ld_out, n, airspeed, tables, wt, af);
+}
+// the same with the nets in GEMM order (contexts with aero_gemm_order)
+__global__ __launch_bounds__(BLOCK) void f16_derived_kernel_gemm(const float *__restrict__ sp, const float *__restrict__ up,
+                                                                 long long ld, float *__restrict__ out, long long ld_out,
+                                                                 long long n, float airspeed, AeroWeights wt, Airframe af) {
+    f16_derived_body<true>(sp, up, ld, out, ld_out, n, airspeed, 0, wt, af);
+}
 
 // hifi_F16.hifi_C / hifi_damping / hifi_C_lef / hifi_damping_lef / hifi_rudder / hifi_ailerons / hifi_other_coeffs
 // (envs/models/F16/hifi_F16_AeroData.py:745-822) for arbitrary (alpha, beta, el) in degrees: the same normalisation and net
 // bodies nlplant runs (so what this returns IS what the step kernels use), out[43][ld_out] in the reference's evaluation order
 // (np_nets.h::NetId).  Row N_dCzq_lef (the net nlplant never reads, F16_dynamics.py:199) is not part of the device weights: 0.
-__global__ __launch_bounds__(BLOCK) void f16_aero_kernel(const float *__restrict__ alpha_deg, const float *__restrict__ beta_deg,
-                                                         const float *__restrict__ el, long long n, float *__restrict__ out,
-                                                         long long ld_out, int tables, AeroWeights wt) {
+template <bool GEMM>
+__device__ __forceinline__ void f16_aero_body(const float *__restrict__ alpha_deg, const float *__restrict__ beta_deg, const float *__restrict__ el,
+                                              long long n, float *__restrict__ out, long long ld_out, int tables, const AeroWeights &wt) {
     __shared__ float lds[NUM_LDS_SLOTS * BLOCK];
     float *coef = lds + threadIdx.x;
     const long long i = (long long)blockIdx.x * BLOCK + threadIdx.x;
@@ -111,7 +122,7 @@ __global__ __launch_bounds__(BLOCK) void f16_aero_kernel(const float *__restrict
     normalise_inputs(wt, a, b, e, xn);
     const float chk = ((a - a) + (b - b)) + (e - e);  // numerics spec: non-finite inputs poison every coefficient
     const bool ok = (chk == chk);
-    eval_nets<BLOCK, AB_ALL, true>(wt, xn, coef, tables != 0);
+    eval_nets<BLOCK, AB_ALL, true, 1, GEMM>(wt, xn, coef, tables != 0);
     if (!valid) return;
     const float qnan = __builtin_nanf("");
 #pragma unroll
@@ -119,6 +130,16 @@ __global__ __launch_bounds__(BLOCK) void f16_aero_kernel(const float *__restrict
         const int slot = slot_of(net);
         out[net * ld_out + i] = slot < 0 ? 0.0f : (ok ? coef[slot * BLOCK] : qnan);
     }
+}
+__global__ __launch_bounds__(BLOCK) void f16_aero_kernel(const float *__restrict__ alpha_deg, const float *__restrict__ beta_deg,
+                                                         const float *__restrict__ el, long long n, float *__restrict__ out,
+                                                         long long ld_out, int tables, AeroWeights wt) {
+    f16_aero_body<false>(alpha_deg, beta_deg, el, n, out, ld_out, tables, wt);
+}
+__global__ __launch_bounds__(BLOCK) void f16_aero_kernel_gemm(const float *__restrict__ alpha_deg, const float *__restrict__ beta_deg,
+                                                              const float *__restrict__ el, long long n, float *__restrict__ out,
+                                                              long long ld_out, AeroWeights wt) {
+    f16_aero_body<true>(alpha_deg, beta_deg, el, n, out, ld_out, 0, wt);
 }
 
 // PlanningEnv.low_level_obs (planning_env.py:60-142): ControlTask-style observation for caller-supplied targets, no noise
@@ -173,18 +194,21 @@ __global__ __launch_bounds__(BLOCK) void f16_lowlevel_obs_kernel(const float *__
 }
 
 // cached coefficients of a reset aircraft (alpha = beta = 0) -> out[14]; run once per context
-__global__ __launch_bounds__(BLOCK) void f16_reset_coef_kernel(float *out, int tables, AeroWeights wt) {
+template <bool GEMM>
+__device__ __forceinline__ void f16_reset_coef_body(float *out, int tables, const AeroWeights &wt) {
     __shared__ float lds[NUM_LDS_SLOTS * BLOCK];
     float *coef = lds + threadIdx.x;
     float xn[NUM_NORM_GROUPS];
     const float r2d = (float)(180.0 / 3.141592653589793);
     normalise_inputs(wt, 0.0f * r2d, 0.0f * r2d, 0.0f, xn);
-    eval_ab<BLOCK, AB_FORCE>(wt, xn, coef, tables != 0);
+    eval_ab<BLOCK, AB_FORCE, GEMM>(wt, xn, coef, tables != 0);
     if (threadIdx.x == 0) {
 #pragma unroll
         for (int k = 0; k < NUM_CACHED; k++) out[k] = coef[cached_slot(k) * BLOCK];
     }
 }
+__global__ __launch_bounds__(BLOCK) void f16_reset_coef_kernel(float *out, int tables, AeroWeights wt) { f16_reset_coef_body<false>(out, tables, wt); }
+__global__ __launch_bounds__(BLOCK) void f16_reset_coef_kernel_gemm(float *out, AeroWeights wt) { f16_reset_coef_body<true>(out, 0, wt); }
 
 // Self-check of the numerics spec's constant division on THIS device: np_divc(x, c) against the IEEE x / c for every one of the
 // 2^32 bit patterns of x.  counts[0]: mismatches whose IEEE quotient is a normal number with |x| >= 2^-100 (the spec promises
@@ -241,6 +265,7 @@ struct np_f16_ctx {
     float *d_reset_coef;  // [NUM_CACHED] device buffer owned by the context
     float *d_weights;     // KBLOB | PWL tables | PWL un-normalisation, one device allocation owned by the context
     AeroWeights wt;
+    bool gemm_order = false;  // cfg.aero_gemm_order: the GEMM-order kernels (f16_env_kernel_gemm) on wt.kblob_gemm
     int variant;          // NP_KERNEL_AUTO / _LATENCY / _THROUGHPUT / _PAIR / _LATENCY8
     bool combat;  // created by np_f16_combat_ctx_create: only the combat entry points accept it
     CombatDevCfg ccfg;
@@ -288,7 +313,7 @@ static_assert(sizeof(BlobRec) == 128, "blob record is 128 bytes");
 
 // asset blob (torch layout W[out][in]) -> kernel-order blob (np_nets.h)
 int pack_kblob(const void *blob, size_t nbytes, std::vector<float> &kb, std::vector<float> &kbd, std::vector<float> &pwl,
-               std::vector<float> &pwl_unnorm) {
+               std::vector<float> &pwl_unnorm, std::vector<float> *kbg = nullptr) {
     const unsigned char *p = (const unsigned char *)blob;
     if (!p || nbytes < 16 || std::memcmp(p, "NPF16MLP", 8) != 0) return fail("weights blob: bad magic");
     uint32_t ver, nn;
@@ -402,6 +427,37 @@ int pack_kblob(const void *blob, size_t nbytes, std::vector<float> &kb, std::vec
             dst += pad2(in + 1);
             dst[0] = src[0];  // out_std
             dst[1] = src[1];  // out_mean
+        }
+    }
+    // the same records in the layout of the GEMM-order bodies (np_nets.h::gemm_record_len): bias rows behind their weight rows, behind the same
+    // header.  The values are those of `kb`, whose exact 2^ACT_SHIFT rescaling was checked above: a blob that cannot be rescaled never gets here.
+    if (kbg) {
+        kbg->assign(KBLOB_GEMM_FLOATS, 0.0f);
+        for (int k = 0; k < KBLOB_HEADER; k++) (*kbg)[k] = kb[k];
+        for (int cl = 0; cl < NUM_CLASSES; cl++) {
+            const NetClass c = CLASSES[cl];
+            const int hid[3] = {c.h1, c.h2, c.h3};
+            const int n_hidden = c.h3 > 0 ? 3 : 2;
+            for (int m = 0; m < c.count; m++) {
+                const float *src = kb.data() + class_base(cl) + (size_t)m * class_stride(cl);
+                float *dst = kbg->data() + gemm_class_base(cl) + (size_t)m * gemm_class_stride(cl);
+                int in = c.n_in;
+                for (int l = 0; l < n_hidden; l++) {
+                    const int out = hid[l], row = pad2(out);
+                    for (int k = 0; k < in; k++)
+                        for (int j = 0; j < out; j++) dst[row * k + j] = src[row * (k + 1) + j];  // W[j][k]
+                    for (int j = 0; j < out; j++) dst[row * in + j] = src[j];                   // bias[j]
+                    src += (size_t)row * (in + 1);
+                    dst += (size_t)row * (in + 1);
+                    in = out;
+                }
+                for (int k = 0; k < in; k++) dst[k] = src[2 + k];  // W[0][k]
+                dst[pad2(in)] = src[0];                            // bias; dst[pad2(in) + 1] stays 0
+                src += 2 + pad2(in);
+                dst += pad2(in) + 2;
+                dst[0] = src[0];  // out_std
+                dst[1] = src[1];  // out_mean
+            }
         }
     }
     // PWL section (blob v2): "PWL1", n_tables, seg_cap, then {net_index, n_segments, t[64], a[64], x0[64], c[64]}
@@ -695,7 +751,7 @@ int launch_env(np_f16_ctx *ctx, int64_t n, const np_f16_io *io, void *stream) {
     // four-wave variant's single generation (both numerics; Euler).  latency4w: four waves per tile at four waves per SIMD, one generation
     // of four tiles per CU (MLP numerics; the table mode's kernels are not built for it).
     const npdispatch::EnvChoice ch = npdispatch::env_choice(n, ctx->num_cus, STEP, ctx->solver, ctx->cfg.aero_1d_tables != 0, ctx->variant,
-                                                            env_kernel_override(), pair_waves_override(), BLOCK);
+                                                            env_kernel_override(), pair_waves_override(), BLOCK, ctx->gemm_order);
     const bool pair = ch.pair, latency = ch.latency, latency8 = ch.latency8, latency2 = ch.latency2, latency4w = ch.latency4w;
     const dim3 grid((unsigned)ch.grid), block((unsigned)ch.block);
     a.cus = ctx->num_cus;
@@ -721,8 +777,14 @@ int launch_env(np_f16_ctx *ctx, int64_t n, const np_f16_io *io, void *stream) {
     l.a = a; l.grid = grid.x; l.block = block.x; l.st = st; l.timed = timed; l.start = ev.first; l.stop = ev.second;
     l.step = STEP; l.inner = STEP && a.inner; l.cached = cached;
     l.pair = pair; l.pair3 = pair3; l.latency = latency; l.latency8 = latency8; l.latency2 = latency2; l.latency4w = latency4w;
-    const int key = ctx->task * 2 + (STEP ? ctx->solver : 0);
+    const int key = ctx->task * 2 + (STEP ? ctx->solver : 0) + (ctx->gemm_order ? 6 : 0);
     switch (key) {
+    case 6: env_dispatch_gemm_t0s0(l); break;
+    case 7: env_dispatch_gemm_t0s1(l); break;
+    case 8: env_dispatch_gemm_t1s0(l); break;
+    case 9: env_dispatch_gemm_t1s1(l); break;
+    case 10: env_dispatch_gemm_t2s0(l); break;
+    case 11: env_dispatch_gemm_t2s1(l); break;
     case 0: env_dispatch_t0s0(l); break;
     case 1: env_dispatch_t0s1(l); break;
     case 2: env_dispatch_t1s0(l); break;
@@ -866,12 +928,20 @@ void np_f16_airframe_default(np_f16_airframe *out) {
     if (out) *out = airframe_defaults();
 }
 
+static int dispatch_plan_impl(int64_t n, int32_t num_cus, int32_t step, int32_t solver, int32_t tables, int32_t gemm, int32_t variant, np_dispatch_info *out);
 int np_dispatch_plan(int64_t n, int32_t num_cus, int32_t step, int32_t solver, int32_t tables, int32_t variant, np_dispatch_info *out) {
+    return dispatch_plan_impl(n, num_cus, step, solver, tables, 0, variant, out);
+}
+int np_dispatch_plan_gemm(int64_t n, int32_t num_cus, int32_t step, int32_t solver, int32_t variant, np_dispatch_info *out) {
+    if (variant == NP_KERNEL_PAIR) return fail("np_dispatch_plan_gemm: aero_gemm_order has no pair family (NP_KERNEL_PAIR)");
+    return dispatch_plan_impl(n, num_cus, step, solver, 0, 1, variant, out);
+}
+static int dispatch_plan_impl(int64_t n, int32_t num_cus, int32_t step, int32_t solver, int32_t tables, int32_t gemm, int32_t variant, np_dispatch_info *out) {
     if (!out) return fail("null argument");
     if (n <= 0 || num_cus <= 0) return fail("np_dispatch_plan: n and num_cus must be positive");
     if (variant < NP_KERNEL_AUTO || variant > NP_KERNEL_DUAL4) return fail("np_dispatch_plan: unknown variant");
     const bool dual_pin = variant == NP_KERNEL_DUAL8 || variant == NP_KERNEL_DUAL4;   // SingleCombat only: the env kernels keep their size rule
-    const npdispatch::EnvChoice c = npdispatch::env_choice(n, num_cus, step != 0, solver, tables != 0, dual_pin ? NP_KERNEL_AUTO : variant, NP_KERNEL_AUTO, 0, BLOCK);
+    const npdispatch::EnvChoice c = npdispatch::env_choice(n, num_cus, step != 0, solver, tables != 0, dual_pin ? NP_KERNEL_AUTO : variant, NP_KERNEL_AUTO, 0, BLOCK, gemm != 0);
     const npdispatch::Limits l = npdispatch::limits_for(num_cus);
     out->pair = c.pair; out->pair3 = c.pair3; out->latency = c.latency; out->latency8 = c.latency8; out->latency2 = c.latency2;
     out->latency4w = c.latency4w; out->block = c.block; out->grid = c.grid;
@@ -880,9 +950,18 @@ int np_dispatch_plan(int64_t n, int32_t num_cus, int32_t step, int32_t solver, i
     const int dual = !(step && solver == 0 && !tables) ? 0 : dual_pin ? (variant == NP_KERNEL_DUAL8 ? 8 : 4)
                      : variant == NP_KERNEL_AUTO ? npdispatch::combat_dual_waves(n, num_cus) : 0;
     out->combat_latency = dual == 8 ? 2 : dual == 4 ? 3 : n <= l.combat_lat_max_n ? 1 : 0;
-    out->planning_mode = npdispatch::planning_mode(n, num_cus);   // one eight-wave workgroup per CU
-    out->planning_mode_i8 = npdispatch::planning_mode(n, num_cus, true);
+    out->planning_mode = gemm ? (int)npdispatch::PL_LAUNCHES : npdispatch::planning_mode(n, num_cus);   // one eight-wave workgroup per CU
+    out->planning_mode_i8 = gemm ? (int)npdispatch::PL_LAUNCHES : npdispatch::planning_mode(n, num_cus, true);
     return 0;
+}
+int64_t np_f16_pack_kblob_gemm(const void *weights_blob, size_t nbytes, float *out, int64_t cap) {
+    std::vector<float> kb, kbd, pwl, pwl_unnorm, kbg;
+    if (pack_kblob(weights_blob, nbytes, kb, kbd, pwl, pwl_unnorm, &kbg)) return -1;
+    if (out) {
+        if (cap < (int64_t)kbg.size()) return fail("np_f16_pack_kblob_gemm: output buffer too small") ? -1 : -1;
+        std::memcpy(out, kbg.data(), kbg.size() * sizeof(float));
+    }
+    return (int64_t)kbg.size();
 }
 int64_t np_f16_cache_floats(int64_t n) { return n <= 0 ? 0 : ((n + BLOCK - 1) / BLOCK) * (int64_t)BLOCK * NUM_CACHE_ROWS; }
 const char *np_last_error(void) { return g_err.c_str(); }
@@ -890,9 +969,9 @@ const char *np_last_error(void) { return g_err.c_str(); }
 int np_internal_fail(const char *msg) { return fail(msg ? msg : "unknown error"); }
 extern "C" {
 
-static int ctx_create_common(const void *weights_blob, size_t nbytes, int tables, int device, np_f16_ctx **out) {
-    std::vector<float> kb, kbd, pwl, pwl_unnorm;
-    if (pack_kblob(weights_blob, nbytes, kb, kbd, pwl, pwl_unnorm)) return 1;
+static int ctx_create_common(const void *weights_blob, size_t nbytes, int tables, int device, np_f16_ctx **out, bool gemm = false) {
+    std::vector<float> kb, kbd, pwl, pwl_unnorm, kbg;
+    if (pack_kblob(weights_blob, nbytes, kb, kbd, pwl, pwl_unnorm, gemm ? &kbg : nullptr)) return 1;
     if (tables && pwl.empty()) return fail("cfg.aero_1d_tables needs a version-2 weights blob (PWL section)");
     int ndev = 0;
     NP_HIP(hipGetDeviceCount(&ndev));
@@ -907,9 +986,11 @@ static int ctx_create_common(const void *weights_blob, size_t nbytes, int tables
     const size_t n_kb = KBLOB_FLOATS, n_pwl = (size_t)NUM_PWL_TABLES * PWL_TABLE_FLOATS, n_un = (size_t)NUM_PWL_TABLES * 2;
     const size_t off_dual = (n_kb + n_pwl + n_un + 63) / 64 * 64;  // 256-byte aligned
     float *d_w = nullptr, *d_rc = nullptr;
-    NP_HIP(hipMalloc(&d_w, sizeof(float) * (off_dual + KBLOB_DUAL_FLOATS)));
+    const size_t off_gemm = (off_dual + KBLOB_DUAL_FLOATS + 63) / 64 * 64;  // the GEMM-order records: contexts with aero_gemm_order only
+    NP_HIP(hipMalloc(&d_w, sizeof(float) * (gemm ? off_gemm + KBLOB_GEMM_FLOATS : off_dual + KBLOB_DUAL_FLOATS)));
     hipError_t e0 = hipMemcpy(d_w, kb.data(), sizeof(float) * n_kb, hipMemcpyHostToDevice);
     if (e0 == hipSuccess) e0 = hipMemcpy(d_w + off_dual, kbd.data(), sizeof(float) * KBLOB_DUAL_FLOATS, hipMemcpyHostToDevice);
+    if (e0 == hipSuccess && gemm) e0 = hipMemcpy(d_w + off_gemm, kbg.data(), sizeof(float) * KBLOB_GEMM_FLOATS, hipMemcpyHostToDevice);
     if (e0 == hipSuccess && !pwl.empty()) {
         e0 = hipMemcpy(d_w + n_kb, pwl.data(), sizeof(float) * n_pwl, hipMemcpyHostToDevice);
         if (e0 == hipSuccess) e0 = hipMemcpy(d_w + n_kb + n_pwl, pwl_unnorm.data(), sizeof(float) * n_un, hipMemcpyHostToDevice);
@@ -919,10 +1000,12 @@ static int ctx_create_common(const void *weights_blob, size_t nbytes, int tables
     wt.kblob_dual = d_w + off_dual;
     wt.pwl = pwl.empty() ? nullptr : d_w + n_kb;
     wt.pwl_unnorm = pwl.empty() ? nullptr : d_w + n_kb + n_pwl;
+    wt.kblob_gemm = gemm ? d_w + off_gemm : nullptr;
     hipError_t e1 = e0 == hipSuccess ? hipMalloc(&d_rc, sizeof(float) * NUM_CACHED) : e0;
     hipError_t e2 = hipSuccess, e3 = hipSuccess;
     if (e1 == hipSuccess) {  // coefficients of a reset aircraft, evaluated by the device code itself (bit-identical to in-line evaluation)
-        hipLaunchKernelGGL(f16_reset_coef_kernel, dim3(1), dim3(BLOCK), 0, 0, d_rc, tables ? 1 : 0, wt);
+        if (gemm) hipLaunchKernelGGL(f16_reset_coef_kernel_gemm, dim3(1), dim3(BLOCK), 0, 0, d_rc, wt);
+        else hipLaunchKernelGGL(f16_reset_coef_kernel, dim3(1), dim3(BLOCK), 0, 0, d_rc, tables ? 1 : 0, wt);
         e2 = hipGetLastError();
         e3 = hipDeviceSynchronize();
     }
@@ -942,6 +1025,7 @@ static int ctx_create_common(const void *weights_blob, size_t nbytes, int tables
     ctx->d_reset_coef = d_rc;
     ctx->d_weights = d_w;
     ctx->wt = wt;
+    ctx->gemm_order = gemm;
     ctx->timing = false;
     ctx->t_sum_ms = 0.0;
     ctx->t_count = 0;
@@ -961,7 +1045,9 @@ int np_f16_ctx_create(const void *weights_blob, size_t nbytes, const np_f16_cfg 
     if (cfg->solver < 0 || cfg->solver > 1) return fail("cfg.solver must be NP_SOLVER_EULER/RK4");
     if (!airframe_is_zero(cfg->airframe))
         if (const char *e = airframe_error(cfg->airframe)) return fail(e);
-    if (ctx_create_common(weights_blob, nbytes, cfg->aero_1d_tables, device, out)) return 1;
+    if (cfg->aero_gemm_order && cfg->aero_1d_tables)
+        return fail("cfg.aero_gemm_order and cfg.aero_1d_tables exclude each other (the tables replace the chains whose order aero_gemm_order sets)");
+    if (ctx_create_common(weights_blob, nbytes, cfg->aero_1d_tables, device, out, cfg->aero_gemm_order != 0)) return 1;
     (*out)->task = cfg->task;
     (*out)->solver = cfg->solver;
     (*out)->cfg = make_devcfg(*cfg);
@@ -975,6 +1061,7 @@ int np_f16_combat_ctx_create(const void *weights_blob, size_t nbytes, const np_f
     if (cfg->solver < 0 || cfg->solver > 1) return fail("cfg.solver must be NP_SOLVER_EULER/RK4");
     if (cfg->inner_steps < 1 || cfg->inner_steps > 16) return fail("cfg.inner_steps must be in 1..16");
     if (!(cfg->dt > 0.0)) return fail("cfg.dt must be positive");
+    if (cfg->aero_gemm_order) return fail("cfg.aero_gemm_order: SingleCombat has no GEMM-order kernels (two-set bodies only); the field must be 0");
     if (!airframe_is_zero(cfg->airframe))
         if (const char *e = airframe_error(cfg->airframe)) return fail(e);
     if (ctx_create_common(weights_blob, nbytes, cfg->aero_1d_tables, device, out)) return 1;
@@ -1042,6 +1129,10 @@ int np_f16_derived(np_f16_ctx *ctx, int64_t n, const float *s, const float *u, i
     DeviceGuard guard;
     NP_HIP(guard.enter(ctx->device));
     const dim3 grid((unsigned)((n + BLOCK - 1) / BLOCK)), block(BLOCK);
+    if (ctx->gemm_order)
+        hipLaunchKernelGGL(f16_derived_kernel_gemm, grid, block, 0, (hipStream_t)stream, s, u, (long long)ld, out, (long long)ld_out, (long long)n,
+                           ctx->cfg.airspeed, ctx->wt, ctx->cfg.af);
+    else
     hipLaunchKernelGGL(f16_derived_kernel, grid, block, 0, (hipStream_t)stream, s, u, (long long)ld, out, (long long)ld_out,
                        (long long)n, ctx->cfg.airspeed, ctx->cfg.aero_1d_tables, ctx->wt, ctx->combat ? ctx->ccfg.af : ctx->cfg.af);
     NP_HIP(hipGetLastError());
@@ -1056,6 +1147,9 @@ int np_f16_aero_coefficients(np_f16_ctx *ctx, int64_t n, const float *alpha_deg,
     DeviceGuard guard;
     NP_HIP(guard.enter(ctx->device));
     const dim3 grid((unsigned)((n + BLOCK - 1) / BLOCK)), block(BLOCK);
+    if (ctx->gemm_order)
+        hipLaunchKernelGGL(f16_aero_kernel_gemm, grid, block, 0, (hipStream_t)stream, alpha_deg, beta_deg, el, (long long)n, out, (long long)ld_out, ctx->wt);
+    else
     hipLaunchKernelGGL(f16_aero_kernel, grid, block, 0, (hipStream_t)stream, alpha_deg, beta_deg, el, (long long)n, out,
                        (long long)ld_out, ctx->cfg.aero_1d_tables, ctx->wt);
     NP_HIP(hipGetLastError());
@@ -1454,7 +1548,7 @@ int np_planning_inner_loop(np_f16_ctx *ctx, int64_t n, const np_f16_io *io, cons
                    : std::strcmp(e, "queue") == 0 ? NP_PLANNING_PERSISTENT_QUEUE : std::strcmp(e, "guests") == 0 ? NP_PLANNING_PERSISTENT_GUESTS : std::strcmp(e, "dual") == 0 ? NP_PLANNING_PERSISTENT_DUAL : mode;
         }
         if (const char *e = std::getenv("NP_PLANNING_WAVES")) waves = atoi(e) == 8 ? 8 : atoi(e) == 4 ? 4 : waves;
-        const bool eligible = ctx->solver == 0 && !ctx->cfg.aero_1d_tables && io->coef_cache && !io->rand_u && !io->noise && io->reward && planning_persistent_built(ctx->task);
+        const bool eligible = ctx->solver == 0 && !ctx->cfg.aero_1d_tables && !ctx->gemm_order && io->coef_cache && !io->rand_u && !io->noise && io->reward && planning_persistent_built(ctx->task);
         if (mode >= NP_PLANNING_PERSISTENT && !eligible)
             return fail("np_planning_loop: the persistent kernel serves tracking contexts (the reference's PlanningEnv task) with the Euler solver and the MLP numerics, and needs coef_cache / reward buffers");
         if (mode == NP_PLANNING_AUTO) {
@@ -1705,6 +1799,8 @@ int np_f16_set_kernel_variant(np_f16_ctx *ctx, int variant) {
     } else if (variant != NP_KERNEL_AUTO && variant != NP_KERNEL_LATENCY && variant != NP_KERNEL_THROUGHPUT && variant != NP_KERNEL_PAIR &&
                variant != NP_KERNEL_LATENCY8 && variant != NP_KERNEL_LATENCY2 && variant != NP_KERNEL_LATENCY4W)
         return fail("unknown kernel variant");
+    if (ctx->gemm_order && variant == NP_KERNEL_PAIR)
+        return fail("NP_KERNEL_PAIR: a context with aero_gemm_order has single-set kernels only (throughput and latency variants)");
     ctx->variant = variant;
     return 0;
 }

@@ -205,6 +205,34 @@ constexpr int dual_class_base(int cl) {
     return off;
 }
 constexpr int KBLOB_DUAL_FLOATS = dual_class_base(NUM_CLASSES) + 2 * ASM_GROUP;
+// ---- third record layout, for the single-set bodies in GEMM order (numerics option aero_gemm_order, np_mlp_asm_gemm.inc) ----------
+// There every chain starts with a multiply and the bias is added LAST (acc = W[j][0] x[0]; fma ...; acc + bias[j]; the oracle's
+// MODE_BIAS_LAST), so the bias row moves behind the weight rows it closes.  Record of one net (floats):
+//   per hidden layer (in -> out):  for k < in: W[.][k] as a row of `out` weights (+pad to even), then bias[out] (+pad to even)
+//   output layer (in -> 1):        W[0][0..in) (+pad to even), then (bias, 0) — ONE chain, not the spec's two half-chains
+//   out_std, out_mean, zero padding to whole weight-stream groups.
+// A permutation of the first layout's record (same values, same 2^-ACT_SHIFT scaling, same length), behind the same header: class bases,
+// phase starts and the normalisation constants sit where they sit in the KBLOB.  np_pack_kblob derives it from the first.
+constexpr int gemm_record_len(int n_in, int h1, int h2, int h3) {
+    int n = n_in * pad2(h1) + pad2(h1) + h1 * pad2(h2) + pad2(h2);
+    if (h3 > 0) n += h2 * pad2(h3) + pad2(h3) + pad2(h3) + 2;
+    else n += pad2(h2) + 2;  // output layer: W[0][0..in) padded to even, then the (bias, 0) pair
+    n += 2;  // out_std, out_mean
+    return (n + ASM_GROUP - 1) / ASM_GROUP * ASM_GROUP;
+}
+constexpr int gemm_class_stride(int cl) { return gemm_record_len(CLASSES[cl].n_in, CLASSES[cl].h1, CLASSES[cl].h2, CLASSES[cl].h3); }
+constexpr int gemm_class_base(int cl) {
+    int off = KBLOB_HEADER;
+    for (int k = 0; k < cl; k++) off += CLASSES[k].count * gemm_class_stride(k);
+    return off;
+}
+constexpr int KBLOB_GEMM_FLOATS = gemm_class_base(NUM_CLASSES) + 2 * ASM_GROUP;
+constexpr bool gemm_layout_matches() {
+    for (int cl = 0; cl <= NUM_CLASSES; cl++)
+        if (gemm_class_base(cl) != class_base(cl)) return false;
+    return true;
+}
+static_assert(gemm_layout_matches() && KBLOB_GEMM_FLOATS == KBLOB_FLOATS, "the GEMM-order records are permutations of the first layout's records");
 static_assert(class_slot(NUM_CLASSES) == NUM_LIVE_NETS, "every live net belongs to exactly one class");
 static_assert(class_slot(NUM_AB_CLASSES) == NUM_AB_NETS, "alpha/beta-only nets occupy slots 0..35");
 constexpr int num_force_ab() {

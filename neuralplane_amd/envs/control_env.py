@@ -10,8 +10,8 @@ class ControlEnv(BaseEnv):
     """Fly-control env: one F-16 per agent, tasks heading / control / tracking."""
 
     def __init__(self, num_envs=1, config='heading', model='F16', random_seed=None, device='cuda:0', row0=0,
-                 aero_1d_tables=None, solver=None, weights=None, airframe=None):
-        super().__init__(num_envs, config, model, random_seed, device, row0=row0, aero_1d_tables=aero_1d_tables, solver=solver,
+                 aero_1d_tables=None, solver=None, weights=None, airframe=None, aero_gemm_order=None):
+        super().__init__(num_envs, config, model, random_seed, device, row0=row0, aero_1d_tables=aero_1d_tables, aero_gemm_order=aero_gemm_order, solver=solver,
                          weights=weights, airframe=airframe)
 
     def load(self, random_seed, config, model):

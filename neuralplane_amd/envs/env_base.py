@@ -14,7 +14,7 @@ from .utils.utils import parse_config
 
 class BaseEnv(Env):
     def __init__(self, num_envs=10, config='heading', model='F16', random_seed=None, device='cuda:0', row0=0,
-                 aero_1d_tables=None, solver=None, weights=None, airframe=None):
+                 aero_1d_tables=None, solver=None, weights=None, airframe=None, aero_gemm_order=None):
         """airframe (not a reference argument): {np_f16_airframe field: value} for every constant that differs from the F-16's — mass, Jx,
         Jy, Jz, Jxz, S, B, cbar, xcg, xcgr, Heng, g, ail_ref, rud_ref, the atmosphere and command scales (include/neuralplane_amd.h) —,
         or the scenario YAML's `airframe:` mapping; together with `weights` (another NPF16MLP blob of the same topology) that is another
@@ -30,6 +30,7 @@ class BaseEnv(Env):
         self.create_records = False
         self._row0 = row0
         self._aero_1d_tables = aero_1d_tables  # numerics option; None -> scenario key / env var / off
+        self._aero_gemm_order = aero_gemm_order  # numerics option: the aero MLPs in GEMM order; None -> scenario key / NPF16_AERO_GEMM_ORDER / off
         self._weights = weights                # None -> the shipped F-16 blob; else the path of another NPF16MLP blob (same topology)
         self._solver = solver                  # None -> the scenario's `solver` key ('euler' | 'rk4', F16_model.py:16)
         self.load(random_seed, config, model)
@@ -43,7 +44,8 @@ class BaseEnv(Env):
         seed = 0 if random_seed is None else int(random_seed)
         self._batch = F16Batch(self.n, self.config, task, self.device, seed=seed, row0=self._row0,
                                aero_1d_tables=self._aero_1d_tables, solver=self._solver,
-                               **({'blob_path': self._weights} if self._weights else {}))
+                               **({'blob_path': self._weights} if self._weights else {}),
+                               **({'aero_gemm_order': self._aero_gemm_order} if self._aero_gemm_order is not None else {}))
         self.device = self._batch.device
         return self._batch
 

@@ -19,9 +19,11 @@ from .utils.utils import parse_config
 
 
 class SingleCombatEnv(Env):
-    def __init__(self, num_envs=1, config='selfplay', random_seed=None, device='cuda:0', env0=0, aero_1d_tables=None, airframe=None):
+    def __init__(self, num_envs=1, config='selfplay', random_seed=None, device='cuda:0', env0=0, aero_1d_tables=None, airframe=None, aero_gemm_order=None):
         super().__init__()
         self.config = parse_config(config)
+        if aero_gemm_order or getattr(self.config, 'aero_gemm_order', 0):
+            raise ValueError('aero_gemm_order: SingleCombatEnv has no GEMM-order kernels (its kernels run the two-set bodies); leave the option off')
         if airframe is not None:        # {np_f16_airframe field: value}: see BaseEnv
             self.config.airframe = dict(airframe)
         self.num_envs = num_envs

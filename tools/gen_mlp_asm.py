@@ -546,12 +546,107 @@ def gen_dual_file():
     print('wrote np_mlp_asm_dual.inc')
 
 
-def gen_function(shape):
+# ------------------------------------------------------------------------------------------------
+# GEMM order (numerics option aero_gemm_order, np_mlp_asm_gemm.inc): every Linear layer as a finished dot product plus bias,
+#     acc = W[j][0] * x[0]; acc = fma(W[j][k], x[k], acc), k = 1 .. in-1; acc = acc + bias[j]
+# — the order of a GEMM with a bias epilogue (the oracle's MODE_BIAS_LAST).  One accumulator set, the weight streaming of Body.
+# The first term of a chain is a v_pk_mul_f32 (w * x rounds exactly as fma(w, x, +0) does), so no accumulator is initialised by a
+# move; one packed bias add per neuron pair closes the chains of a hidden layer and carries the ReLU as its `clamp` (same
+# 2^-ACT_SHIFT scaled activations as the spec bodies); the output layer is ONE serial chain (v_mul_f32, v_fmac_f32 ..., bias add).
+# Record layout of one net (np_nets.h::gemm_record_len; the values are those of the first layout, np_pack_kblob permutes them):
+#   per hidden layer (in -> out):  for k < in: W[.][k] as a row of `out` weights (+pad to even), then bias[out] (+pad to even)
+#   output layer (in -> 1):        W[0][0..in) (+pad to even), then (bias, 0)
+#   out_std, out_mean, zero padding to whole groups.  Same length as the first layout: class bases and phase starts coincide.
+# ------------------------------------------------------------------------------------------------
+class BodyGemm(Body):
+    def dense(self, n_in, n_out, in_regs, out_base):
+        row = pad2(n_out)
+        p0 = self.pos
+        for k in range(n_in):
+            pk = p0 + row * k
+            xr = in_regs[k]
+            e = xr & 1
+            xp = self.vpair(xr - e)
+            for j in range(0, n_out - 1, 2):
+                sp = self.spair(pk + j)
+                acc = self.vpair(out_base + j)
+                if k == 0:
+                    self.ins.append(f'v_pk_mul_f32 {acc}, {sp}, {xp} op_sel:[0,{e}] op_sel_hi:[1,{e}]')
+                else:
+                    self.ins.append(f'v_pk_fma_f32 {acc}, {sp}, {xp}, {acc} op_sel:[0,{e},0] op_sel_hi:[1,{e},1]')
+            if n_out & 1:
+                j = n_out - 1
+                s_w = self.s1(pk + j)
+                self.ins.append(f'v_mul_f32 v{out_base + j}, {s_w}, v{xr}' if k == 0 else f'v_fmac_f32 v{out_base + j}, {s_w}, v{xr}')
+        pb = p0 + row * n_in
+        # bias last; ReLU = the clamp modifier of the bias add (activations carried / 2^ACT_SHIFT: the upper bound 1.0 is 2^40)
+        for j in range(0, n_out - 1, 2):
+            acc = self.vpair(out_base + j)
+            self.ins.append(f'v_pk_add_f32 {acc}, {self.spair(pb + j)}, {acc} clamp')
+        if n_out & 1:
+            j = n_out - 1
+            self.ins.append(f'v_add_f32 v{out_base + j}, {self.s1(pb + j)}, v{out_base + j} clamp')
+        self.pos = p0 + row * (n_in + 1)
+
+    def final(self, n_in, in_regs):
+        """output layer in -> 1 as ONE chain: y = W[0] * x[0]; y = fma(W[k], x[k], y); y = y + bias"""
+        p0 = self.pos
+        for k in range(n_in):
+            s_w = self.s1(p0 + k)
+            self.ins.append(f'v_mul_f32 v{V_Y}, {s_w}, v{in_regs[k]}' if k == 0 else f'v_fmac_f32 v{V_Y}, {s_w}, v{in_regs[k]}')
+        self.pos = p0 + pad2(n_in)
+        self.ins.append(f'v_add_f32 v{V_Y}, {self.s1(self.pos)}, v{V_Y}')
+        self.pos += 2
+        # unnormalize: X * std + mean, two roundings (hifi_F16_AeroData.py:36-37)
+        self.ins.append(f'v_mul_f32 v{V_Y}, {self.s1(self.pos)}, v{V_Y}')
+        self.ins.append(f'v_add_f32 v{V_Y}, {self.s1(self.pos + 1)}, v{V_Y}')
+        self.pos += 2
+
+
+def gen_gemm_text():
+    out = ['// GENERATED by tools/gen_mlp_asm.py (BodyGemm) — do not edit.',
+           '// Single-set class and phase bodies in GEMM order (numerics option aero_gemm_order): chains start with a multiply, the bias is added last.',
+           '#pragma once', '']
+    for shape in SHAPES:
+        lines, _ = gen_function(shape, BodyGemm, 'mlp_class_asm_gemm')
+        out += lines
+    out.append('// record lengths the generator assumed (checked against np_nets.h::gemm_record_len)')
+    for IN, H1, H2, H3 in SHAPES:
+        out.append(f'static_assert(gemm_record_len({IN}, {H1}, {H2}, {H3}) == {record_len(IN, H1, H2, H3)}, "KBLOB_GEMM record layout");')
+    out.append('static_assert(gemm_class_base(NUM_CLASSES) == class_base(NUM_CLASSES) && KBLOB_GEMM_FLOATS == KBLOB_FLOATS, "KBLOB_GEMM: class bases of the first layout");')
+    out.append('')
+    out.append('template <int IN, int H1, int H2, int H3, int COUNT, int LDS_STEP>')
+    out.append('__device__ __forceinline__ void mlp_class_asm_gemm(const float *w, unsigned lds_addr, float x0, float x1, float x2) {')
+    for i, (IN, H1, H2, H3) in enumerate(SHAPES):
+        kw = 'if' if i == 0 else 'else if'
+        out.append(f'    {kw} constexpr (IN == {IN} && H1 == {H1} && H2 == {H2} && H3 == {H3}) '
+                   f'mlp_class_asm_gemm_{IN}_{H1}_{H2}_{H3}<COUNT, LDS_STEP>(w, lds_addr, x0, x1, x2);')
+    out.append('    else static_assert(IN < 0, "no GEMM-order asm body for this MLP shape");')
+    out.append('}')
+    out.append('')
+    for kind in ('ALL', 'REST', 'FORCE2'):
+        out += gen_phase(kind, BodyGemm, 'mlp_phase_asm_gemm', 'MLP_PHASE_GEMM')
+    return '\n'.join(out) + '\n'
+
+
+def gen_gemm_file(outdir=None):
+    """np_mlp_asm_gemm.inc is NOT committed (0.9 MB of generated text): neuralplane_amd/build.py calls this before it compiles, and the file is
+    rewritten only when its text changes (so an up-to-date build stays up to date)."""
+    path = os.path.join(outdir or CSRC, 'np_mlp_asm_gemm.inc')
+    txt = gen_gemm_text()
+    if not (os.path.exists(path) and open(path).read() == txt):
+        with open(path, 'w') as f:
+            f.write(txt)
+        print('wrote np_mlp_asm_gemm.inc')
+    return path
+
+
+def gen_function(shape, body_cls=Body, prefix='mlp_class_asm'):
     IN, H1, H2, H3 = shape
     ln = record_len(*shape)
     ngroups = ln // GROUP
     two_parities = ngroups % 2 == 1
-    name = f'mlp_class_asm_{IN}_{H1}_{H2}_{H3}'
+    name = f'{prefix}_{IN}_{H1}_{H2}_{H3}'
     lines = []
     A = lines.append
     A(f'// shape {IN}-{H1}-{H2}' + (f'-{H3}' if H3 else '') + f'-1: record {ln} floats = {ngroups} groups'
@@ -576,7 +671,7 @@ def gen_function(shape):
         emit(f's_load_dwordx16 s[{S_W0 + 16 * c}:{S_W0 + 16 * c + 15}], s[{S_BASE}:{S_BASE + 1}], 0x{c * 64:x}')
     emit('.LNP_LOOP_%=:')
     for parity in ([0, 1] if two_parities else [0]):
-        for ins in Body(shape, parity).build():
+        for ins in body_cls(shape, parity).build():
             emit(ins)
         emit(f'ds_write_b32 v{V_ADDR}, v{V_Y}')
         emit(f'v_add_u32 v{V_ADDR}, %[step], v{V_ADDR}')
@@ -656,9 +751,9 @@ def phase_items(kind):
     return [it for it in items if it[2] > 0]
 
 
-def gen_phase(kind):
+def gen_phase(kind, body_cls=Body, prefix='mlp_phase_asm', const_prefix='MLP_PHASE'):
     items = phase_items(kind)
-    name = f'mlp_phase_asm_{kind}'
+    name = f'{prefix}_{kind}'
     lines = []
     A = lines.append
     A(f'// phase {kind}: ' + ', '.join(f'{CLASSES[ci][0]}[{first}:{first + n}]' for ci, first, n in items))
@@ -705,7 +800,7 @@ def gen_phase(kind):
                 emit(f's_cmov_b32 s{S_NEXT}, 0x{delta * 4:x}')
             emit(f's_add_u32 s{S_NEXT}, s{S_BASE}, s{S_NEXT}')
             emit(f's_addc_u32 s{S_NEXT + 1}, s{S_BASE + 1}, 0')
-            for ins in Body(shape, par, use_next=True).build():
+            for ins in body_cls(shape, par, use_next=True).build():
                 emit(ins)
             emit(f'ds_write_b32 v{V_ADDR}, v{V_Y}')
             emit(f'v_add_u32 v{V_ADDR}, %[step], v{V_ADDR}')
@@ -729,7 +824,7 @@ def gen_phase(kind):
     A('}')
     A('')
     first_off = class_base(items[0][0]) + items[0][1] * record_len(*CLASSES[items[0][0]][1])
-    A(f'constexpr int MLP_PHASE_{kind}_START = {first_off};  // KBLOB offset of the first record of the phase')
+    A(f'constexpr int {const_prefix}_{kind}_START = {first_off};  // KBLOB offset of the first record of the phase')
     A('')
     return lines
 
@@ -1155,6 +1250,7 @@ def main():
 if __name__ == '__main__':
     main()
     gen_dual_file()
+    gen_gemm_file()
     gen_actor_dense()
     gen_actor_mfma_file()
     gen_actor_mfma16_file()

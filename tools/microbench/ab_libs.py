@@ -2,7 +2,7 @@
 """A/B timing of kernel builds INSIDE ONE gpurun session (box-to-box spread is +-3-5 %): every tools/microbench/libs/*.so
 (or the names given) runs the headline workload in its own process through NPF16_LIB, interleaved over `--rounds` rounds.
 
-    python tools/microbench/ab_libs.py [--rounds 2] [--n 1000000] [--steps 100] [name ...]
+    python tools/microbench/ab_libs.py [--rounds 2] [--n 1000000] [--steps 100] [name ...]      (name+gemm: that library with aero_gemm_order on)
 
 Build variants in the build container, e.g.
     NPF16_EXTRA_FLAGS="-DNPF16_EXP=1" python -c "from neuralplane_amd import build; build.build_hip(force=True)"
@@ -34,7 +34,11 @@ def main():
     res = {n: [] for n in names}
     for _ in range(args.rounds):
         for n in names:
-            env = dict(os.environ, NPF16_LIB=os.path.join(LIBS, n + '.so'))
+            # `name+gemm`: the library `name` with the numerics option aero_gemm_order switched on for the run (NPF16_AERO_GEMM_ORDER=1)
+            lib_name, _, opt = n.partition('+')
+            env = dict(os.environ, NPF16_LIB=os.path.join(LIBS, lib_name + '.so'))
+            if opt == 'gemm':
+                env['NPF16_AERO_GEMM_ORDER'] = '1'
             cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--headline-only', '--steps', str(args.steps), '--warmup', '5', '--n', str(args.n),
                    '--task', args.task] + args.extra.split()
             r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
