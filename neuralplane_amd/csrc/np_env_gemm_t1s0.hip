@@ -1,4 +1,4 @@
-// np_env_gemm_t1s0.hip — the instantiations of f16_env_kernel_gemm (np_f16_env_kernel.h: the env kernels with the aero nets in GEMM
+// np_env_gemm_t1s0.hip — the instantiations of f16_env_kernel<..., GEMM = true> (np_f16_env_kernel.h: the env kernels with the aero nets in GEMM
 // order, numerics option aero_gemm_order) for task 1 (0 heading, 1 control, 2 tracking) and solver 0 (0 euler, 1 rk4).
 #define NP_ENV_TASK 1
 #define NP_ENV_SOLVER 0

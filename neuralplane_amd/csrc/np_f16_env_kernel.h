@@ -1,14 +1,9 @@
 // np_f16_env_kernel.h — the fused F-16 env.step / env.reset kernel template (reference: envs/env_base.py:83-109), shared by the
-// translation units that instantiate it: np_env_t{0,1,2}s{0,1}.hip (one per task x solver, built in parallel; np_env_tu.inc) — the host
-// side (context, dispatch rule, C ABI) is np_f16_kernels.hip, which hands a launch over through np_env_launch.h.
-// This header is included ONCE for f16_env_kernel and, in the units of the GEMM-order kernels (np_env_tu.inc with NP_ENV_GEMM), a SECOND time with
-// NP_ENV_KERNEL_NAME = f16_env_kernel_gemm and NP_ENV_KERNEL_GEMM = true: the same kernel text with the aero nets in GEMM order (numerics option
-// aero_gemm_order) as a kernel template of its own — never a run-time branch, and f16_env_kernel stays, token for token, the kernel it was.
-#ifndef NP_F16_ENV_KERNEL_H
-#define NP_F16_ENV_KERNEL_H
-#define NP_ENV_KERNEL_NAME f16_env_kernel
-#define NP_ENV_KERNEL_GEMM false
-#define NP_F16_ENV_KERNEL_FIRST_PASS
+// translation units that instantiate it: np_env_t{0,1,2}s{0,1}.hip and np_env_gemm_t{0,1,2}s{0,1}.hip (one per task x solver x GEMM, built in
+// parallel; np_env_tu.inc) — the host side (context, dispatch rule, C ABI) is np_f16_kernels.hip, which hands a launch over through
+// np_env_launch.h.  The numerics option aero_gemm_order (the aero nets in GEMM order) is the kernel's last template parameter, GEMM: a
+// compile-time constant of the instantiation, never a run-time branch; the np_env_gemm_* units instantiate the single-set family with it.
+#pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
@@ -54,11 +49,6 @@ namespace npf16 {
 #ifndef NPF16_STAGGER_CYCLES_LONG
 #define NPF16_STAGGER_CYCLES_LONG 30000  // grids of 8 generations and more (N >= 1.6e6 on 256 CUs), see the kernel
 #endif
-#endif  // NP_F16_ENV_KERNEL_H (the preamble)
-#ifndef NP_F16_ENV_KERNEL_FIRST_PASS
-namespace npf16 {
-#endif
-#undef NP_F16_ENV_KERNEL_FIRST_PASS
 
 // STEP=true : BaseEnv.step  (env_base.py:99-109)
 // STEP=false: BaseEnv.reset (env_base.py:83-97)
@@ -74,13 +64,13 @@ namespace npf16 {
 //                                  lone wave's time; wave 0 stores.
 // INNER     : one low-level iteration of PlanningEnv.step (np_f16_io.inner_step): no auto-reset, flagged rows keep their state, flags
 //             accumulate.  A template parameter so that the plain env.step carries none of its selects (~30 VALU instructions).
-template <int TASK, int SOLVER, bool STEP, bool CACHED, int TILE = BLOCK, int WPT = 1, bool INNER = false, int PW = 2>
+// GEMM      : numerics option aero_gemm_order (np_f16_device.h::eval_class); single-set bodies only, so never with WPT = 2.
+template <int TASK, int SOLVER, bool STEP, bool CACHED, int TILE = BLOCK, int WPT = 1, bool INNER = false, int PW = 2, bool GEMM = false>
 // waves per SIMD the register allocator builds for: pair variant PW (PW = 2 is also an occupancy CAP — 159 VGPRs would fit three — for the
 // grid sizes where six workgroups per CU are placed unevenly), latency4w four, everything else NPF16_MINWAVES
 __global__ __launch_bounds__(TILE * lat_waves(WPT))
 __attribute__((amdgpu_waves_per_eu((WPT == 2 ? PW : (WPT == 4 && PW == 4) ? 4 : NPF16_MINWAVES), (WPT == 2 && PW == 2 ? 2 : 8))))
-void NP_ENV_KERNEL_NAME(const KArgs a) {
-    constexpr bool GEMM = NP_ENV_KERNEL_GEMM;  // numerics option aero_gemm_order (np_f16_device.h::eval_class), a compile-time constant of this instantiation
+void f16_env_kernel(const KArgs a) {
     // latency variant with shared scalar work (Euler step): wave w computes a quarter of the tile's serial fp64 chains and of its
     // observation noise for ALL four waves (np_f16_device.h::nlplant<.., SHARE>), wave 0 finishes the observation, wave 1 the
     // terminations / reward / state stores

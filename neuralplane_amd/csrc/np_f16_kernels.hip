@@ -38,13 +38,17 @@ hipError_t launch_actor_i8(const float *weights, long long n, const float *obs, 
 
 namespace npf16 {
 
-// f16_env_kernel<TASK, SOLVER, STEP, CACHED, TILE, WPT, INNER, PW>: np_f16_env_kernel.h (instantiated by np_env_t*s*.hip, launched through
-// np_env_launch.h::env_dispatch — one translation unit per task x solver so that the library builds in parallel)
+// f16_env_kernel<TASK, SOLVER, STEP, CACHED, TILE, WPT, INNER, PW, GEMM>: np_f16_env_kernel.h (instantiated by np_env_t*s*.hip and
+// np_env_gemm_t*s*.hip, launched through np_env_launch.h::env_dispatch<TASK, SOLVER, GEMM> — one translation unit per task x solver x GEMM so
+// that the library builds in parallel)
 
 
 // F16Model getters that need the dynamics or the atmosphere (F16_model.py:47-49, 132-198): out[23][ld_out]
+// GEMM: the nets in GEMM order (contexts with aero_gemm_order; no table mode there: `tables` is ignored)
+// The rows are computed by a device function of their own: inlined, its __restrict__ parameters reach the instruction scheduler as alias scopes,
+// which the qualifiers of a kernel's own parameters do not (f16_aero_kernel: 7 instructions and ~1 % at a million rows).
 template <bool GEMM>
-__device__ __forceinline__ void f16_derived_body(const float *__restrict__ sp, const float *__restrict__ up, long long ld, float *__restrict__ out,
+__device__ __forceinline__ void f16_derived_rows(const float *__restrict__ sp, const float *__restrict__ up, long long ld, float *__restrict__ out,
                                                  long long ld_out, long long n, float airspeed, int tables, const AeroWeights &wt, const Airframe &af) {
     __shared__ float lds[NUM_LDS_SLOTS * BLOCK];
     float *coef = lds + threadIdx.x;
@@ -61,7 +65,7 @@ __device__ __forceinline__ void f16_derived_body(const float *__restrict__ sp, c
     trig_of(s, tr, tt);
     np_sincos(s[5], spsi, cpsi);
     float xd[12];
-    nlplant<true, AB_ALL, BLOCK, 1, GEMM>(wt, af, s, u, tr, tt, spsi, cpsi, coef, tables != 0, xd);
+    nlplant<true, AB_ALL, BLOCK, 1, GEMM>(wt, af, s, u, tr, tt, spsi, cpsi, coef, GEMM ? false : tables != 0, xd);
     float a3[3];
     body_acceleration(s, tr, xd, a3);
     const float inv_grav = (float)(1.0 / 32.174), minv_grav = (float)(-1.0 / 32.174);  // F16_model.py:166,176-178
@@ -93,24 +97,20 @@ __device__ __forceinline__ void f16_derived_body(const float *__restrict__ sp, c
     out[21 * ld_out + i] = qbar;
     out[22 * ld_out + i] = ps;
 }
+template <bool GEMM>
 __global__ __launch_bounds__(BLOCK) void f16_derived_kernel(const float *__restrict__ sp, const float *__restrict__ up,
                                                             long long ld, float *__restrict__ out, long long ld_out,
                                                             long long n, float airspeed, int tables, AeroWeights wt, Airframe af) {
-    f16_derived_body<false>(sp, up, ld, out, ld_out, n, airspeed, tables, wt, af);
-}
-// the same with the nets in GEMM order (contexts with aero_gemm_order)
-__global__ __launch_bounds__(BLOCK) void f16_derived_kernel_gemm(const float *__restrict__ sp, const float *__restrict__ up,
-                                                                 long long ld, float *__restrict__ out, long long ld_out,
-                                                                 long long n, float airspeed, AeroWeights wt, Airframe af) {
-    f16_derived_body<true>(sp, up, ld, out, ld_out, n, airspeed, 0, wt, af);
+    f16_derived_rows<GEMM>(sp, up, ld, out, ld_out, n, airspeed, tables, wt, af);
 }
 
 // hifi_F16.hifi_C / hifi_damping / hifi_C_lef / hifi_damping_lef / hifi_rudder / hifi_ailerons / hifi_other_coeffs
 // (envs/models/F16/hifi_F16_AeroData.py:745-822) for arbitrary (alpha, beta, el) in degrees: the same normalisation and net
 // bodies nlplant runs (so what this returns IS what the step kernels use), out[43][ld_out] in the reference's evaluation order
 // (np_nets.h::NetId).  Row N_dCzq_lef (the net nlplant never reads, F16_dynamics.py:199) is not part of the device weights: 0.
+// GEMM, and the device function: as f16_derived_kernel.
 template <bool GEMM>
-__device__ __forceinline__ void f16_aero_body(const float *__restrict__ alpha_deg, const float *__restrict__ beta_deg, const float *__restrict__ el,
+__device__ __forceinline__ void f16_aero_rows(const float *__restrict__ alpha_deg, const float *__restrict__ beta_deg, const float *__restrict__ el,
                                               long long n, float *__restrict__ out, long long ld_out, int tables, const AeroWeights &wt) {
     __shared__ float lds[NUM_LDS_SLOTS * BLOCK];
     float *coef = lds + threadIdx.x;
@@ -122,7 +122,7 @@ __device__ __forceinline__ void f16_aero_body(const float *__restrict__ alpha_de
     normalise_inputs(wt, a, b, e, xn);
     const float chk = ((a - a) + (b - b)) + (e - e);  // numerics spec: non-finite inputs poison every coefficient
     const bool ok = (chk == chk);
-    eval_nets<BLOCK, AB_ALL, true, 1, GEMM>(wt, xn, coef, tables != 0);
+    eval_nets<BLOCK, AB_ALL, true, 1, GEMM>(wt, xn, coef, GEMM ? false : tables != 0);
     if (!valid) return;
     const float qnan = __builtin_nanf("");
 #pragma unroll
@@ -131,15 +131,11 @@ __device__ __forceinline__ void f16_aero_body(const float *__restrict__ alpha_de
         out[net * ld_out + i] = slot < 0 ? 0.0f : (ok ? coef[slot * BLOCK] : qnan);
     }
 }
+template <bool GEMM>
 __global__ __launch_bounds__(BLOCK) void f16_aero_kernel(const float *__restrict__ alpha_deg, const float *__restrict__ beta_deg,
                                                          const float *__restrict__ el, long long n, float *__restrict__ out,
                                                          long long ld_out, int tables, AeroWeights wt) {
-    f16_aero_body<false>(alpha_deg, beta_deg, el, n, out, ld_out, tables, wt);
-}
-__global__ __launch_bounds__(BLOCK) void f16_aero_kernel_gemm(const float *__restrict__ alpha_deg, const float *__restrict__ beta_deg,
-                                                              const float *__restrict__ el, long long n, float *__restrict__ out,
-                                                              long long ld_out, AeroWeights wt) {
-    f16_aero_body<true>(alpha_deg, beta_deg, el, n, out, ld_out, 0, wt);
+    f16_aero_rows<GEMM>(alpha_deg, beta_deg, el, n, out, ld_out, tables, wt);
 }
 
 // PlanningEnv.low_level_obs (planning_env.py:60-142): ControlTask-style observation for caller-supplied targets, no noise
@@ -195,20 +191,18 @@ __global__ __launch_bounds__(BLOCK) void f16_lowlevel_obs_kernel(const float *__
 
 // cached coefficients of a reset aircraft (alpha = beta = 0) -> out[14]; run once per context
 template <bool GEMM>
-__device__ __forceinline__ void f16_reset_coef_body(float *out, int tables, const AeroWeights &wt) {
+__global__ __launch_bounds__(BLOCK) void f16_reset_coef_kernel(float *out, int tables, AeroWeights wt) {
     __shared__ float lds[NUM_LDS_SLOTS * BLOCK];
     float *coef = lds + threadIdx.x;
     float xn[NUM_NORM_GROUPS];
     const float r2d = (float)(180.0 / 3.141592653589793);
     normalise_inputs(wt, 0.0f * r2d, 0.0f * r2d, 0.0f, xn);
-    eval_ab<BLOCK, AB_FORCE, GEMM>(wt, xn, coef, tables != 0);
+    eval_ab<BLOCK, AB_FORCE, GEMM>(wt, xn, coef, GEMM ? false : tables != 0);
     if (threadIdx.x == 0) {
 #pragma unroll
         for (int k = 0; k < NUM_CACHED; k++) out[k] = coef[cached_slot(k) * BLOCK];
     }
 }
-__global__ __launch_bounds__(BLOCK) void f16_reset_coef_kernel(float *out, int tables, AeroWeights wt) { f16_reset_coef_body<false>(out, tables, wt); }
-__global__ __launch_bounds__(BLOCK) void f16_reset_coef_kernel_gemm(float *out, AeroWeights wt) { f16_reset_coef_body<true>(out, 0, wt); }
 
 // Self-check of the numerics spec's constant division on THIS device: np_divc(x, c) against the IEEE x / c for every one of the
 // 2^32 bit patterns of x.  counts[0]: mismatches whose IEEE quotient is a normal number with |x| >= 2^-100 (the spec promises
@@ -265,7 +259,7 @@ struct np_f16_ctx {
     float *d_reset_coef;  // [NUM_CACHED] device buffer owned by the context
     float *d_weights;     // KBLOB | PWL tables | PWL un-normalisation, one device allocation owned by the context
     AeroWeights wt;
-    bool gemm_order = false;  // cfg.aero_gemm_order: the GEMM-order kernels (f16_env_kernel_gemm) on wt.kblob_gemm
+    bool gemm_order = false;  // cfg.aero_gemm_order: the GEMM = true instantiations of the kernels, on wt.kblob_gemm
     int variant;          // NP_KERNEL_AUTO / _LATENCY / _THROUGHPUT / _PAIR / _LATENCY8
     bool combat;  // created by np_f16_combat_ctx_create: only the combat entry points accept it
     CombatDevCfg ccfg;
@@ -752,8 +746,6 @@ int launch_env(np_f16_ctx *ctx, int64_t n, const np_f16_io *io, void *stream) {
     // of four tiles per CU (MLP numerics; the table mode's kernels are not built for it).
     const npdispatch::EnvChoice ch = npdispatch::env_choice(n, ctx->num_cus, STEP, ctx->solver, ctx->cfg.aero_1d_tables != 0, ctx->variant,
                                                             env_kernel_override(), pair_waves_override(), BLOCK, ctx->gemm_order);
-    const bool pair = ch.pair, latency = ch.latency, latency8 = ch.latency8, latency2 = ch.latency2, latency4w = ch.latency4w;
-    const dim3 grid((unsigned)ch.grid), block((unsigned)ch.block);
     a.cus = ctx->num_cus;
     hipStream_t st = (hipStream_t)stream;
     // Pair variant at three waves per SIMD (six workgroups per CU) or at two (four per CU)?  Measured per grid size (heading,
@@ -764,7 +756,6 @@ int launch_env(np_f16_ctx *ctx, int64_t n, const np_f16_io *io, void *stream) {
     // to every three-wave grid (round 3, see the kernel) it wins there too (229 376 aircraft 124.2 -> 88.9 us, 327 680 126.4 ->
     // 118.9; profiles/r03f_mid_large_n.log).  PlanningEnv's inner steps take the same rule since the end of round 3 (165 VGPRs, no
     // scratch; the macro-step at n = 150 000: 29.2 -> 27.6 ms, 262 144: 45.8 -> 44.2 ms, profiles/r03f_planning_inner_pair3.log).
-    const bool pair3 = ch.pair3;
     if (io->cache_valid && !io->coef_cache) return fail("cache_valid set without a coef_cache buffer");
     const bool cached = STEP && io->coef_cache && io->cache_valid;
     const bool timed = STEP && ctx->timing && !stream_is_capturing(st);  // event-attached dispatches cannot be captured into a graph
@@ -772,27 +763,18 @@ int launch_env(np_f16_ctx *ctx, int64_t n, const np_f16_io *io, void *stream) {
     if (timed && ctx->events.size() >= MAX_PENDING_EVENTS && resolve_events(ctx)) return 1;  // a caller that never polls
     if (timed) NP_HIP(lease.take());
     const std::pair<hipEvent_t, hipEvent_t> &ev = lease.ev;
-    // the kernels live in one translation unit per task x solver (np_env_t*s*.hip, np_env_launch.h); a reset has no solver: Euler unit
+    // the kernels live in one translation unit per task x solver x GEMM (np_env_t*s*.hip, np_env_gemm_t*s*.hip; np_env_launch.h); a reset has no
+    // solver: Euler unit
     EnvLaunch l;
-    l.a = a; l.grid = grid.x; l.block = block.x; l.st = st; l.timed = timed; l.start = ev.first; l.stop = ev.second;
+    l.a = a; l.ch = ch; l.st = st; l.timed = timed; l.start = ev.first; l.stop = ev.second;
     l.step = STEP; l.inner = STEP && a.inner; l.cached = cached;
-    l.pair = pair; l.pair3 = pair3; l.latency = latency; l.latency8 = latency8; l.latency2 = latency2; l.latency4w = latency4w;
-    const int key = ctx->task * 2 + (STEP ? ctx->solver : 0) + (ctx->gemm_order ? 6 : 0);
-    switch (key) {
-    case 6: env_dispatch_gemm_t0s0(l); break;
-    case 7: env_dispatch_gemm_t0s1(l); break;
-    case 8: env_dispatch_gemm_t1s0(l); break;
-    case 9: env_dispatch_gemm_t1s1(l); break;
-    case 10: env_dispatch_gemm_t2s0(l); break;
-    case 11: env_dispatch_gemm_t2s1(l); break;
-    case 0: env_dispatch_t0s0(l); break;
-    case 1: env_dispatch_t0s1(l); break;
-    case 2: env_dispatch_t1s0(l); break;
-    case 3: env_dispatch_t1s1(l); break;
-    case 4: env_dispatch_t2s0(l); break;
-    case 5: env_dispatch_t2s1(l); break;
-    default: return fail("bad task/solver");
-    }
+    using Fn = void (*)(const EnvLaunch &);
+    static constexpr Fn table[2][3][2] = {   // [gemm][task][solver]
+        {{env_dispatch<0, 0, false>, env_dispatch<0, 1, false>}, {env_dispatch<1, 0, false>, env_dispatch<1, 1, false>}, {env_dispatch<2, 0, false>, env_dispatch<2, 1, false>}},
+        {{env_dispatch<0, 0, true>, env_dispatch<0, 1, true>}, {env_dispatch<1, 0, true>, env_dispatch<1, 1, true>}, {env_dispatch<2, 0, true>, env_dispatch<2, 1, true>}}};
+    const int solver = STEP ? ctx->solver : 0;
+    if (ctx->task < 0 || ctx->task > 2 || solver < 0 || solver > 1) return fail("bad task/solver");
+    table[ctx->gemm_order ? 1 : 0][ctx->task][solver](l);
     NP_HIP(hipGetLastError());
     if (timed) lease.commit();
     return 0;
@@ -1004,8 +986,7 @@ static int ctx_create_common(const void *weights_blob, size_t nbytes, int tables
     hipError_t e1 = e0 == hipSuccess ? hipMalloc(&d_rc, sizeof(float) * NUM_CACHED) : e0;
     hipError_t e2 = hipSuccess, e3 = hipSuccess;
     if (e1 == hipSuccess) {  // coefficients of a reset aircraft, evaluated by the device code itself (bit-identical to in-line evaluation)
-        if (gemm) hipLaunchKernelGGL(f16_reset_coef_kernel_gemm, dim3(1), dim3(BLOCK), 0, 0, d_rc, wt);
-        else hipLaunchKernelGGL(f16_reset_coef_kernel, dim3(1), dim3(BLOCK), 0, 0, d_rc, tables ? 1 : 0, wt);
+        hipLaunchKernelGGL((gemm ? f16_reset_coef_kernel<true> : f16_reset_coef_kernel<false>), dim3(1), dim3(BLOCK), 0, 0, d_rc, tables ? 1 : 0, wt);
         e2 = hipGetLastError();
         e3 = hipDeviceSynchronize();
     }
@@ -1129,12 +1110,8 @@ int np_f16_derived(np_f16_ctx *ctx, int64_t n, const float *s, const float *u, i
     DeviceGuard guard;
     NP_HIP(guard.enter(ctx->device));
     const dim3 grid((unsigned)((n + BLOCK - 1) / BLOCK)), block(BLOCK);
-    if (ctx->gemm_order)
-        hipLaunchKernelGGL(f16_derived_kernel_gemm, grid, block, 0, (hipStream_t)stream, s, u, (long long)ld, out, (long long)ld_out, (long long)n,
-                           ctx->cfg.airspeed, ctx->wt, ctx->cfg.af);
-    else
-    hipLaunchKernelGGL(f16_derived_kernel, grid, block, 0, (hipStream_t)stream, s, u, (long long)ld, out, (long long)ld_out,
-                       (long long)n, ctx->cfg.airspeed, ctx->cfg.aero_1d_tables, ctx->wt, ctx->combat ? ctx->ccfg.af : ctx->cfg.af);
+    hipLaunchKernelGGL((ctx->gemm_order ? f16_derived_kernel<true> : f16_derived_kernel<false>), grid, block, 0, (hipStream_t)stream, s, u,
+                       (long long)ld, out, (long long)ld_out, (long long)n, ctx->cfg.airspeed, ctx->cfg.aero_1d_tables, ctx->wt, ctx->combat ? ctx->ccfg.af : ctx->cfg.af);
     NP_HIP(hipGetLastError());
     return 0;
 }
@@ -1147,11 +1124,8 @@ int np_f16_aero_coefficients(np_f16_ctx *ctx, int64_t n, const float *alpha_deg,
     DeviceGuard guard;
     NP_HIP(guard.enter(ctx->device));
     const dim3 grid((unsigned)((n + BLOCK - 1) / BLOCK)), block(BLOCK);
-    if (ctx->gemm_order)
-        hipLaunchKernelGGL(f16_aero_kernel_gemm, grid, block, 0, (hipStream_t)stream, alpha_deg, beta_deg, el, (long long)n, out, (long long)ld_out, ctx->wt);
-    else
-    hipLaunchKernelGGL(f16_aero_kernel, grid, block, 0, (hipStream_t)stream, alpha_deg, beta_deg, el, (long long)n, out,
-                       (long long)ld_out, ctx->cfg.aero_1d_tables, ctx->wt);
+    hipLaunchKernelGGL((ctx->gemm_order ? f16_aero_kernel<true> : f16_aero_kernel<false>), grid, block, 0, (hipStream_t)stream, alpha_deg, beta_deg,
+                       el, (long long)n, out, (long long)ld_out, ctx->cfg.aero_1d_tables, ctx->wt);
     NP_HIP(hipGetLastError());
     return 0;
 }

@@ -170,6 +170,37 @@ def test_design_kernel_table_is_what_the_library_says():
             assert not any('vcc' in x for x in ins) or '"vcc"' in b.split(':')[-1], f'{name}: vcc written but not declared'
 
 
+def test_env_kernel_instantiations_follow_the_family_rules():
+    """The set of f16_env_kernel instantiations in the built library obeys the three family-level rules np_env_tu.inc encodes: the GEMM-order
+    bodies are single-set (no pair variant, WPT == 2, with GEMM), the latency family (64-aircraft tiles) is built for Euler only, and per task
+    the GEMM family is the non-GEMM family minus the pair variants — so an edit of the dispatch cannot quietly add or drop kernels."""
+    import importlib.util
+    import os
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    from neuralplane_amd import build
+    spec = importlib.util.spec_from_file_location('_code_object_table', os.path.join(root, 'tools', 'code_object_table.py'))
+    cot = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(cot)
+    val = {'true': True, 'false': False}
+    fam = {}   # (task, GEMM) -> {(SOLVER, STEP, CACHED, TILE, WPT, INNER, PW)}
+    for row in cot.kernels_of(build.build_hip()):
+        m = re.fullmatch(r'npf16::f16_env_kernel<(.*)>', cot.kernel_key(row[0]))
+        if not m:
+            continue
+        args = [val[x] if x in val else int(x) for x in m.group(1).split(', ')]
+        assert len(args) == 9, row[0]
+        task, solver, step, cached, tile, wpt, inner, pw, gemm = args
+        assert not (wpt == 2 and gemm), f'{row[0]}: pair variant with GEMM-order bodies'
+        assert not (solver == 1 and tile == 64), f'{row[0]}: rk4 latency kernel'
+        variant = (solver, step, cached, tile, wpt, inner, pw)
+        assert variant not in fam.setdefault((task, gemm), set()), f'{row[0]}: instantiated twice'
+        fam[(task, gemm)].add(variant)
+    assert sorted(fam) == [(t, g) for t in range(3) for g in (False, True)]
+    for task in range(3):
+        assert fam[(task, True)] == {v for v in fam[(task, False)] if v[4] != 2}, f'task {task}: GEMM family != non-GEMM family minus the pair variants'
+
+
 def test_two_set_phase_statements_by_emulation():
     """The generated pair-variant statements (np_mlp_asm_dual.inc: ~20 000 lines of inline asm) executed as TEXT by
     tools/emulate_dual_asm.py — scalar control flow, weight stream, packed FMAs with op_sel / clamp, LDS traffic — on a synthetic
