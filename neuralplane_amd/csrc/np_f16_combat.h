@@ -16,29 +16,7 @@
 
 namespace npf16 {
 
-struct PidDev {
-    float Kp, Ki, Kd, Kff, Kimax, tau, rmax_pos, rmax_neg;
-    int ki_on;  // `self.Ki != 0 and self.dt > 0` (pid.py:38)
-};
-
-struct CombatDevCfg {
-    float dt;        // integrator step t1 - t0 (F16_model.py:66)
-    float dt_pid;    // Controller(dt=...) (singlecombat_env.py:46)
-    float airspeed;
-    float altitude_limit, acceleration_limit, max_velocity, min_velocity;
-    float min_alpha, max_alpha, min_beta, max_beta;
-    float dist_limit_sq;
-    long long max_steps;
-    float init_T;
-    float alt_span, min_altitude, vt_span, min_vt, yaw_span, min_heading, npos_span, min_npos, epos_span, min_epos;
-    PidDev roll, pitch, yaw;
-    float roll_ff, gravity, scale_min, scale_max;
-    int inner_steps;
-    int aero_1d_tables;
-    Airframe af;   // np_f16_combat_cfg.airframe (defaults: the F-16 literals)
-};
-
-struct CombatArgs;
+struct CombatArgs;   // (its PidDev / CombatDevCfg: np_f16_types.h)
 typedef const CombatArgs __attribute__((address_space(4))) *CombatArgsC;
 #ifndef NP_REREAD_ARGS
 #define NP_REREAD_ARGS(ap) asm volatile("" : "+s"(ap) : : "memory")

@@ -12,38 +12,16 @@
 
 #include "np_math.h"
 #include "np_nets.h"
+#include "np_f16_types.h"
 
 namespace npf16 {
 
-// The packed weights of one aircraft type (np_nets.h KBLOB layout + the optional PWL tables) live in device buffers owned
-// by a context, so contexts with different weight sets (a second aircraft with the same net topology) coexist on a device.
-// device code reads them through the CONSTANT address space (read-only for the lifetime of a launch): invariant loads the
-// compiler may reorder, scalarise and merge exactly as it did when the data were __constant__ symbols
+// Device code reads the packed weights (AeroWeights, np_f16_types.h) through the CONSTANT address space (read-only for the lifetime of a
+// launch): invariant loads the compiler may reorder, scalarise and merge exactly as it did when the data were __constant__ symbols
 typedef const float __attribute__((address_space(4))) *cf32_ptr;
 #define NPF16_CONST(p) ((cf32_ptr)(unsigned long long)(p))
-struct AeroWeights {
-    const float *kblob;       // [KBLOB_FLOATS]
-    const float *kblob_dual;  // [KBLOB_DUAL_FLOATS] the same nets in the record layout of the two-set bodies (np_nets.h)
-    const float *pwl;         // [NUM_PWL_TABLES * PWL_TABLE_FLOATS] or null
-    const float *pwl_unnorm;  // [NUM_PWL_TABLES * 2] or null
-    const float *kblob_gemm;  // [KBLOB_GEMM_FLOATS] the records of the GEMM-order bodies (np_nets.h), or null: contexts with aero_gemm_order only
-};
 
-// The airframe as data (np_f16_airframe, ABI 16): what F16Dynamics.nlplant / atmos and F16Model.update spell as literals
-// (envs/models/F16/F16_dynamics.py:22-35,61-76,114-116; envs/models/F16_model.py:52-62), rounded to fp32 on the host exactly where the
-// literal expressions round (derived constants folded in double first: np_f16_kernels.hip::make_airframe).  r_* = RN(1 / x) of a divisor
-// (np_divc).  The defaults are the F-16 literals: a context built without an airframe block computes what the literals computed, bit for bit.
-struct Airframe {
-    float g, mass, r_mass, B, S, cbar, Heng, pad_;
-    float Jy, r_Jy, Jxz, Jz, Jx;
-    float xc, cbar_over_B, c1, c2, c3, c4, denom, r_denom;       // xcgr - xcg, cbar / B, the inertia products of the moment equations
-    float ail_ref, r_ail_ref, rud_ref, r_rud_ref;                 // dail = ail / 21.5, drud = rud / 30
-    float atm_lapse, rho0;                                        // tfac = 1 - 0.703e-5 alt; rho = 2.377e-3 tfac^4.14
-    double atm_exp;                                               // (double)(float)4.14: the double np_pow computes in; > 0 (host check)
-    float lag_keep, lag_new, thrust_frac, thrust_max, thrust_unit, r_thrust_unit, surf_max[3];   // u' = 0.9 u + 0.1 a * scale
-    __device__ __forceinline__ const Airframe &get() const { return *this; }
-};
-// How nlplant reaches the airframe.  Inside the step kernels nothing scalar may stay live across the two MLP phases (asm statements that own
+// How nlplant reaches the airframe (Airframe, np_f16_types.h).  Inside the step kernels nothing scalar may stay live across the two MLP phases (asm statements that own
 // s4-s101), so the constants are (re-)read from the kernel-argument segment AFTER the phase, through the pointer the kernel already keeps
 // for that purpose (`ap`, NP_REREAD_ARGS): ~35 scalar loads per evaluation, no VALU work, no register held across the statement.
 // AirframeVia<AP>{ap}.get() = ap->cfg.af behind such a re-read; a plain `Airframe` (kernels off the hot path) is its own get().
@@ -63,19 +41,6 @@ struct AirframeVia {
 };
 template <class AP>
 __device__ __forceinline__ AirframeVia<AP> airframe_via(AP &ap) { return AirframeVia<AP>{ap}; }
-
-// Scenario constants, pre-rounded on the host exactly where the reference rounds them.
-struct DevCfg {
-    float dt, airspeed, noise_scale;
-    float altitude_limit, acceleration_limit, max_velocity, min_velocity;
-    float min_alpha, max_alpha, min_beta, max_beta;
-    long long max_check_interval, min_check_interval;
-    float init_T, alt_span, min_altitude, vt_span, min_vt;
-    float max_heading_increment, max_pitch_increment, max_velocities_u_increment;
-    float dist_span, min_distance;
-    int aero_1d_tables;  // single-input nets through their piecewise-linear tables instead of the MLP bodies
-    Airframe af;
-};
 
 // ---------------------------------------------------------------------------------------------
 // MLP evaluation — hifi_F16_AeroData.py:12-37 (MLP.forward, normalize, unnormalize)

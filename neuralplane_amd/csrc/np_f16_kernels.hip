@@ -34,6 +34,7 @@ hipError_t launch_actor_i8(const float *weights, long long n, const float *obs, 
                            hipStream_t stream);   // np_actor_i8.hip
 }
 #include "np_dispatch.h"
+#include "np_f16_host.h"
 #include "np_env_launch.h"
 
 namespace npf16 {
@@ -253,30 +254,30 @@ static int fail(const std::string &msg) {
     } while (0)
 
 struct np_f16_ctx {
-    int device;
-    int task, solver;
-    DevCfg cfg;
-    float *d_reset_coef;  // [NUM_CACHED] device buffer owned by the context
-    float *d_weights;     // KBLOB | PWL tables | PWL un-normalisation, one device allocation owned by the context
-    AeroWeights wt;
+    int device = 0;
+    int task = 0, solver = 0;
+    DevCfg cfg{};
+    float *d_reset_coef = nullptr;  // [NUM_CACHED] device buffer owned by the context
+    float *d_weights = nullptr;     // KBLOB | PWL tables | PWL un-normalisation, one device allocation owned by the context
+    AeroWeights wt{};
     bool gemm_order = false;  // cfg.aero_gemm_order: the GEMM = true instantiations of the kernels, on wt.kblob_gemm
-    int variant;          // NP_KERNEL_AUTO / _LATENCY / _THROUGHPUT / _PAIR / _LATENCY8
-    bool combat;  // created by np_f16_combat_ctx_create: only the combat entry points accept it
-    CombatDevCfg ccfg;
-    bool timing;
+    int variant = NP_KERNEL_AUTO;   // NP_KERNEL_AUTO / _LATENCY / _THROUGHPUT / _PAIR / _LATENCY8
+    bool combat = false;  // created by np_f16_combat_ctx_create: only the combat entry points accept it
+    CombatDevCfg ccfg{};
+    bool timing = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> events;  // recorded, not yet read
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pool;
-    double t_sum_ms;
-    int64_t t_count;
+    double t_sum_ms = 0.0;
+    int64_t t_count = 0;
     std::vector<float> samples;  // per-launch durations in launch order since np_f16_set_timing(ctx, 1)
-    unsigned long long *trace;   // np_f16_set_trace
-    int64_t trace_cap;
+    unsigned long long *trace = nullptr;   // np_f16_set_trace
+    int64_t trace_cap = 0;
     // np_planning_inner_loop: streams of row groups 1.. and the fork / join events (created on first use)
     std::vector<hipStream_t> group_streams;
     std::vector<hipEvent_t> group_events;  // [0] fork, [1 + g] join of group g + 1
     // persistent PlanningEnv kernel (np_planning.hip): the (tile, iteration) queue words, owned by the context, grown on demand
-    unsigned *d_queue;
-    int64_t queue_cap;
+    unsigned *d_queue = nullptr;
+    int64_t queue_cap = 0;
     unsigned queue_next = 0, flag_base = 0;   // where the item counter stands / the base of the progress words for the next launch
     bool queue_dirty = true;
     // bounded waits of the guest / queue schedules (round 5): the launch's sticky error word (device), the record the kernel leaves in pinned
@@ -288,292 +289,10 @@ struct np_f16_ctx {
     hipEvent_t plan_done = nullptr;
     bool plan_unchecked = false;
     const char *plan_unchecked_mode = "";
-    int num_cus;  // multiProcessorCount of the context's device
+    int num_cus = 0;  // multiProcessorCount of the context's device
 };
 
 namespace {
-
-#pragma pack(push, 1)
-struct BlobRec {  // NPF16MLP v1 record (tools/export_weights.py)
-    char name[24];
-    uint32_t input_mask, n_linear;
-    uint32_t dims[6];
-    double in_mean[3], in_std[3];
-    double out_mean, out_std;
-    uint32_t param_offset, n_params;
-};
-#pragma pack(pop)
-static_assert(sizeof(BlobRec) == 128, "blob record is 128 bytes");
-
-// asset blob (torch layout W[out][in]) -> kernel-order blob (np_nets.h)
-int pack_kblob(const void *blob, size_t nbytes, std::vector<float> &kb, std::vector<float> &kbd, std::vector<float> &pwl,
-               std::vector<float> &pwl_unnorm, std::vector<float> *kbg = nullptr) {
-    const unsigned char *p = (const unsigned char *)blob;
-    if (!p || nbytes < 16 || std::memcmp(p, "NPF16MLP", 8) != 0) return fail("weights blob: bad magic");
-    uint32_t ver, nn;
-    std::memcpy(&ver, p + 8, 4);
-    std::memcpy(&nn, p + 12, 4);
-    if ((ver != 1 && ver != 2) || nn != NUM_NETS) return fail("weights blob: unsupported version / net count");
-    const size_t hdr = 16 + (size_t)nn * sizeof(BlobRec);
-    if (nbytes < hdr) return fail("weights blob: truncated header");
-    const size_t pfloats = (nbytes - hdr) / 4;
-    std::vector<float> par(pfloats);
-    std::memcpy(par.data(), p + hdr, pfloats * 4);
-    kb.assign(KBLOB_FLOATS, 0.0f);
-    bool grp_set[NUM_NORM_GROUPS] = {};
-    for (int cl = 0; cl < NUM_CLASSES; cl++) {
-        const NetClass c = CLASSES[cl];
-        const int hid[3] = {c.h1, c.h2, c.h3};
-        const int n_hidden = c.h3 > 0 ? 3 : 2;
-        for (int m = 0; m < c.count; m++) {
-            const int net = c.nets[m];
-            BlobRec r;
-            std::memcpy(&r, p + 16 + (size_t)net * sizeof(BlobRec), sizeof(r));
-            const std::string nm(r.name, strnlen(r.name, sizeof(r.name)));
-            if ((int)r.n_linear != n_hidden + 1 || (int)r.dims[0] != c.n_in) return fail("weights blob: shape of net " + nm + " does not match its class");
-            for (int l = 0; l < n_hidden; l++)
-                if ((int)r.dims[l + 1] != hid[l]) return fail("weights blob: hidden widths of net " + nm + " do not match its class");
-            if ((int)r.n_params != class_params(c)) return fail("weights blob: parameter count of net " + nm);
-            if ((size_t)r.param_offset + r.n_params > pfloats) return fail("weights blob: truncated parameters");
-            // input slot k of the net <- k-th set bit of input_mask (bit0 alpha, bit1 beta, bit2 el)
-            int slot = 0;
-            for (int k = 0; k < 3; k++) {
-                if (!(r.input_mask & (1u << k))) continue;
-                if (slot >= c.n_in) return fail("weights blob: input mask of net " + nm);
-                const int g = c.grp[slot++];
-                const bool kind_ok = (k == 0 && g >= G_A_C && g <= G_A_RUD) || (k == 1 && (g == G_B_C || g == G_B_O)) ||
-                                     (k == 2 && (g == G_E_C || g == G_E_ETA));
-                if (!kind_ok) return fail("weights blob: input kind of net " + nm + " does not match its class");
-                const float mean = (float)r.in_mean[k], sd = (float)r.in_std[k];  // torch rounds the CSV doubles to fp32
-                if (!grp_set[g]) {
-                    kb[KBLOB_NORM_STRIDE * g] = mean;
-                    kb[KBLOB_NORM_STRIDE * g + 1] = sd;
-                    kb[KBLOB_NORM_STRIDE * g + 2] = (float)(1.0 / (double)sd);  // np_divc: the normalisation divides by a per-context constant
-                    grp_set[g] = true;
-                } else if (kb[KBLOB_NORM_STRIDE * g] != mean || kb[KBLOB_NORM_STRIDE * g + 1] != sd) {
-                    return fail("weights blob: normalisation of net " + nm + " differs from its class");
-                }
-            }
-            if (slot != c.n_in) return fail("weights blob: input mask of net " + nm);
-            const float *src = par.data() + r.param_offset;
-            float *dst = kb.data() + class_base(cl) + (size_t)m * class_stride(cl);
-            int in = c.n_in;
-            // Hidden activations are carried divided by 2^ACT_SHIFT (np_nets.h): the ReLU is then the `clamp` output modifier
-            // of the layer's last FMA, which costs no instruction.  Powers of two commute with every rounding, so the first
-            // layer's weights and all hidden biases are stored x 2^-ACT_SHIFT and the output layer's weights x 2^+ACT_SHIFT —
-            // checked here to be exact (normal, finite) for every parameter of the asset.
-            bool exact = true;
-            auto scaled = [&exact](float w, int e) {
-                const float v = std::ldexp(w, e);
-                if (w != 0.0f && !(std::isnormal(v) && std::ldexp(v, -e) == w)) exact = false;
-                return v;
-            };
-            for (int l = 0; l < n_hidden; l++) {  // hidden layers: bias row + `in` weight rows, rows padded to even
-                const int out = hid[l], row = pad2(out);
-                const float *W = src, *bias = src + (size_t)in * out;
-                for (int j = 0; j < out; j++) dst[j] = scaled(bias[j], -ACT_SHIFT);
-                for (int k = 0; k < in; k++)
-                    for (int j = 0; j < out; j++) dst[row * (k + 1) + j] = l == 0 ? scaled(W[j * in + k], -ACT_SHIFT) : W[j * in + k];
-                src += (size_t)in * out + out;
-                dst += (size_t)row * (in + 1);
-                in = out;
-            }
-            {  // output layer in -> 1: (bias, 0), then W[0][0..in) padded to even (two interleaved partial chains, np_nets.h)
-                const float *W = src, *bias = src + in;
-                dst[0] = bias[0];
-                dst[1] = 0.0f;
-                for (int k = 0; k < in; k++) dst[2 + k] = scaled(W[k], ACT_SHIFT);
-                dst += 2 + pad2(in);
-            }
-            if (!exact) return fail("weights blob: a parameter of net " + nm + " cannot be rescaled by 2^ACT_SHIFT exactly");
-            dst[0] = (float)r.out_std;
-            dst[1] = (float)r.out_mean;
-        }
-    }
-    for (int g = 0; g < NUM_NORM_GROUPS; g++)
-        if (!grp_set[g]) return fail("weights blob: a normalisation group is unused");
-    // the same records in the layout of the two-set bodies (np_nets.h::dual_record_len): pure re-arrangement of `kb`
-    kbd.assign(KBLOB_DUAL_FLOATS, 0.0f);
-    for (int cl = 0; cl < NUM_CLASSES; cl++) {
-        const NetClass c = CLASSES[cl];
-        const int hid[3] = {c.h1, c.h2, c.h3};
-        const int n_hidden = c.h3 > 0 ? 3 : 2;
-        for (int m = 0; m < c.count; m++) {
-            const float *src = kb.data() + class_base(cl) + (size_t)m * class_stride(cl);
-            float *dst = kbd.data() + dual_class_base(cl) + (size_t)m * dual_class_stride(cl);
-            int in = c.n_in;
-            for (int l = 0; l < n_hidden; l++) {
-                const int out = hid[l], row = pad2(out);
-                for (int j = 0; j < out; j++) {
-                    dst[2 * j] = src[row + j];  // W[j][0]
-                    dst[2 * j + 1] = src[j];    // bias[j]
-                }
-                for (int k = 1; k < in; k++)
-                    for (int j = 0; j < out; j++) dst[2 * out + (k - 1) * out + j] = src[row * (k + 1) + j];
-                src += (size_t)row * (in + 1);
-                dst += pad2(out * (in + 1));
-                in = out;
-            }
-            dst[0] = src[2];  // W[0][0]
-            dst[1] = src[0];  // bias
-            for (int k = 1; k < in; k++) dst[1 + k] = src[2 + k];
-            src += 2 + pad2(in);
-            dst += pad2(in + 1);
-            dst[0] = src[0];  // out_std
-            dst[1] = src[1];  // out_mean
-        }
-    }
-    // the same records in the layout of the GEMM-order bodies (np_nets.h::gemm_record_len): bias rows behind their weight rows, behind the same
-    // header.  The values are those of `kb`, whose exact 2^ACT_SHIFT rescaling was checked above: a blob that cannot be rescaled never gets here.
-    if (kbg) {
-        kbg->assign(KBLOB_GEMM_FLOATS, 0.0f);
-        for (int k = 0; k < KBLOB_HEADER; k++) (*kbg)[k] = kb[k];
-        for (int cl = 0; cl < NUM_CLASSES; cl++) {
-            const NetClass c = CLASSES[cl];
-            const int hid[3] = {c.h1, c.h2, c.h3};
-            const int n_hidden = c.h3 > 0 ? 3 : 2;
-            for (int m = 0; m < c.count; m++) {
-                const float *src = kb.data() + class_base(cl) + (size_t)m * class_stride(cl);
-                float *dst = kbg->data() + gemm_class_base(cl) + (size_t)m * gemm_class_stride(cl);
-                int in = c.n_in;
-                for (int l = 0; l < n_hidden; l++) {
-                    const int out = hid[l], row = pad2(out);
-                    for (int k = 0; k < in; k++)
-                        for (int j = 0; j < out; j++) dst[row * k + j] = src[row * (k + 1) + j];  // W[j][k]
-                    for (int j = 0; j < out; j++) dst[row * in + j] = src[j];                   // bias[j]
-                    src += (size_t)row * (in + 1);
-                    dst += (size_t)row * (in + 1);
-                    in = out;
-                }
-                for (int k = 0; k < in; k++) dst[k] = src[2 + k];  // W[0][k]
-                dst[pad2(in)] = src[0];                            // bias; dst[pad2(in) + 1] stays 0
-                src += 2 + pad2(in);
-                dst += pad2(in) + 2;
-                dst[0] = src[0];  // out_std
-                dst[1] = src[1];  // out_mean
-            }
-        }
-    }
-    // PWL section (blob v2): "PWL1", n_tables, seg_cap, then {net_index, n_segments, t[64], a[64], x0[64], c[64]}
-    pwl.clear();
-    pwl_unnorm.clear();
-    if (ver >= 2) {
-        size_t n_par = 0;
-        for (int i = 0; i < NUM_NETS; i++) {
-            BlobRec r;
-            std::memcpy(&r, p + 16 + (size_t)i * sizeof(BlobRec), sizeof(r));
-            n_par = std::max(n_par, (size_t)r.param_offset + r.n_params);
-        }
-        const unsigned char *q = p + hdr + n_par * 4, *end = p + nbytes;
-        uint32_t nt, cap;
-        if (q + 12 > end || std::memcmp(q, "PWL1", 4) != 0) return fail("weights blob: PWL section missing");
-        std::memcpy(&nt, q + 4, 4);
-        std::memcpy(&cap, q + 8, 4);
-        if (nt != NUM_PWL_TABLES || cap != PWL_SEG) return fail("weights blob: PWL section shape");
-        q += 12;
-        pwl.assign((size_t)NUM_PWL_TABLES * PWL_TABLE_FLOATS, 0.0f);
-        pwl_unnorm.assign((size_t)NUM_PWL_TABLES * 2, 0.0f);
-        for (uint32_t k = 0; k < nt; k++) {
-            uint32_t idx, nseg;
-            if (q + 8 + PWL_TABLE_FLOATS * 4 > end) return fail("weights blob: truncated PWL section");
-            std::memcpy(&idx, q, 4);
-            std::memcpy(&nseg, q + 4, 4);
-            if (idx >= (uint32_t)NUM_NETS || pwl_index((int)idx) != (int)k || nseg < 1 || nseg > (uint32_t)PWL_SEG)
-                return fail("weights blob: PWL table order does not match the kernel's");
-            std::memcpy(pwl.data() + (size_t)k * PWL_TABLE_FLOATS, q + 8, PWL_TABLE_FLOATS * 4);
-            BlobRec r;
-            std::memcpy(&r, p + 16 + (size_t)idx * sizeof(BlobRec), sizeof(r));
-            pwl_unnorm[2 * k] = (float)r.out_std;
-            pwl_unnorm[2 * k + 1] = (float)r.out_mean;
-            q += 8 + PWL_TABLE_FLOATS * 4;
-        }
-    }
-    return 0;
-}
-
-// np_f16_airframe -> the fp32 constants of the kernels.  Every value is rounded where the literal expression of the reference rounds it:
-// plain literals are Python doubles that enter fp32 tensor arithmetic (one rounding), derived constants are folded in double first
-// (F16_dynamics.py:221-227 evaluates e.g. Jz * (Jz - Jy) + Jxz ** 2 in Python before it meets a tensor).
-np_f16_airframe airframe_defaults() {
-    np_f16_airframe a = {};
-    a.g = 32.17; a.mass = 636.94; a.B = 30.0; a.S = 300.0; a.cbar = 11.32; a.xcgr = 0.35; a.xcg = 0.30; a.Heng = 0.0;
-    a.Jy = 55814.0; a.Jxz = 982.0; a.Jz = 63100.0; a.Jx = 9496.0;
-    a.ail_ref = 21.5; a.rud_ref = 30.0;
-    a.atm_lapse = 0.703e-5; a.atm_exp = 4.14; a.rho0 = 2.377e-3;
-    a.lag_keep = 0.9; a.lag_new = 0.1; a.thrust_frac = 0.225; a.thrust_max = 76300.0; a.thrust_unit = 0.3048;
-    a.surf_max[0] = a.surf_max[1] = a.surf_max[2] = 45.0;
-    return a;
-}
-
-bool airframe_is_zero(const np_f16_airframe &a) {
-    const unsigned char *p = reinterpret_cast<const unsigned char *>(&a);
-    for (size_t k = 0; k < sizeof(a); k++)
-        if (p[k]) return false;
-    return true;
-}
-
-const char *airframe_error(const np_f16_airframe &a) {
-    const double pos[] = {a.mass, a.B, a.S, a.cbar, a.Jy, a.Jz, a.Jx, a.ail_ref, a.rud_ref, a.rho0, a.thrust_unit, a.atm_exp};
-    for (double v : pos)
-        if (!(v > 0.0) || !std::isfinite(v)) return "airframe: mass, B, S, cbar, Jx, Jy, Jz, ail_ref, rud_ref, rho0, thrust_unit and atm_exp must be positive and finite";
-    if (!(a.Jx * a.Jz - a.Jxz * a.Jxz > 0.0)) return "airframe: Jx Jz - Jxz^2 must be positive";
-    const double fin[] = {a.g, a.xcgr, a.xcg, a.Heng, a.Jxz, a.atm_lapse, a.atm_exp, a.lag_keep, a.lag_new, a.thrust_frac, a.thrust_max, a.surf_max[0], a.surf_max[1], a.surf_max[2]};
-    for (double v : fin)
-        if (!std::isfinite(v)) return "airframe: non-finite value";
-    return nullptr;
-}
-
-Airframe make_airframe(const np_f16_airframe &in) {
-    const np_f16_airframe a = airframe_is_zero(in) ? airframe_defaults() : in;
-    auto rcp = [](float c) { return (float)(1.0 / (double)c); };   // NP_RCP_CONST: RN(1 / c) of the fp32 divisor
-    Airframe d;
-    d.g = (float)a.g; d.mass = (float)a.mass; d.r_mass = rcp(d.mass); d.B = (float)a.B; d.S = (float)a.S; d.cbar = (float)a.cbar; d.Heng = (float)a.Heng;
-    d.Jy = (float)a.Jy; d.r_Jy = rcp(d.Jy); d.Jxz = (float)a.Jxz; d.Jz = (float)a.Jz; d.Jx = (float)a.Jx;
-    d.xc = (float)(a.xcgr - a.xcg);
-    d.cbar_over_B = (float)(a.cbar / a.B);
-    d.c1 = (float)(a.Jz * (a.Jz - a.Jy) + a.Jxz * a.Jxz);
-    d.c2 = (float)(a.Jxz * (a.Jx - a.Jy + a.Jz));
-    d.c3 = (float)(a.Jz - a.Jx);
-    d.c4 = (float)(a.Jx * (a.Jx - a.Jy) + a.Jxz * a.Jxz);
-    d.denom = (float)(a.Jx * a.Jz - a.Jxz * a.Jxz);
-    d.r_denom = rcp(d.denom);
-    d.ail_ref = (float)a.ail_ref; d.r_ail_ref = rcp(d.ail_ref); d.rud_ref = (float)a.rud_ref; d.r_rud_ref = rcp(d.rud_ref);
-    d.atm_lapse = (float)a.atm_lapse; d.atm_exp = (double)(float)a.atm_exp; d.rho0 = (float)a.rho0; d.pad_ = 0.0f;
-    d.lag_keep = (float)a.lag_keep; d.lag_new = (float)a.lag_new; d.thrust_frac = (float)a.thrust_frac; d.thrust_max = (float)a.thrust_max;
-    d.thrust_unit = (float)a.thrust_unit; d.r_thrust_unit = rcp(d.thrust_unit);
-    for (int k = 0; k < 3; k++) d.surf_max[k] = (float)a.surf_max[k];
-    return d;
-}
-
-DevCfg make_devcfg(const np_f16_cfg &c) {
-    DevCfg d;
-    d.af = make_airframe(c.airframe);
-    d.dt = (float)c.dt - 0.0f;  // t = tensor([0., dt]); dt = t1 - t0   (F16_model.py:66)
-    d.airspeed = (float)c.airspeed;
-    d.noise_scale = (float)c.noise_scale;
-    d.altitude_limit = (float)c.altitude_limit;
-    d.acceleration_limit = (float)c.acceleration_limit;
-    d.max_velocity = (float)c.max_velocity;
-    d.min_velocity = (float)c.min_velocity;
-    d.min_alpha = (float)c.min_alpha;
-    d.max_alpha = (float)c.max_alpha;
-    d.min_beta = (float)c.min_beta;
-    d.max_beta = (float)c.max_beta;
-    d.max_check_interval = c.max_check_interval;
-    d.min_check_interval = c.min_check_interval;
-    d.init_T = (float)c.init_T;
-    d.alt_span = (float)(c.max_altitude - c.min_altitude);  // Python arithmetic first, then one rounding
-    d.min_altitude = (float)c.min_altitude;
-    d.vt_span = (float)(c.max_vt - c.min_vt);
-    d.min_vt = (float)c.min_vt;
-    d.max_heading_increment = (float)c.max_heading_increment;
-    d.max_pitch_increment = (float)c.max_pitch_increment;
-    d.max_velocities_u_increment = (float)c.max_velocities_u_increment;
-    d.dist_span = (float)(c.max_distance - c.min_distance);
-    d.min_distance = (float)c.min_distance;
-    d.aero_1d_tables = c.aero_1d_tables ? 1 : 0;
-    return d;
-}
 
 struct DeviceGuard {
     int prev = -1;
@@ -615,12 +334,32 @@ int resolve_events(np_f16_ctx *ctx) {
     return 0;
 }
 
+// a launch whose stream is being captured into a HIP graph (PlanningEnv.enable_graph, a caller's torch.cuda.graph)
+bool stream_is_capturing(hipStream_t st) {
+    hipStreamCaptureStatus status = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &status) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    return status != hipStreamCaptureStatusNone;
+}
+
 // A start / stop event pair taken from the context's pool for one timed launch; goes back to the pool unless the launch was
 // enqueued (commit() hands it to ctx->events, where np_f16_get_timing resolves it)
 struct EventLease {
     np_f16_ctx *ctx;
     std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};
+    bool timed = false;
     explicit EventLease(np_f16_ctx *c) : ctx(c) {}
+    // The env / combat launchers' preamble: a step of a context that is being timed gets a pair, unless its stream is being captured
+    // (event-attached dispatches cannot be captured into a graph).  0, or 1 with the error set
+    int begin(bool step, hipStream_t st) {
+        timed = step && ctx->timing && !stream_is_capturing(st);
+        if (!timed) return 0;
+        if (ctx->events.size() >= MAX_PENDING_EVENTS && resolve_events(ctx)) return 1;  // a caller that never polls
+        NP_HIP(take());
+        return 0;
+    }
     hipError_t take() {
         if (!ctx->pool.empty()) {
             ev = ctx->pool.back();
@@ -636,24 +375,14 @@ struct EventLease {
         }
         return e;
     }
-    void commit() {
-        ctx->events.push_back(ev);
+    void commit() {   // nothing to hand over when no pair was taken
+        if (ev.first) ctx->events.push_back(ev);
         ev = {nullptr, nullptr};
     }
     ~EventLease() {
         if (ev.first) ctx->pool.push_back(ev);
     }
 };
-
-// a launch whose stream is being captured into a HIP graph (PlanningEnv.enable_graph, a caller's torch.cuda.graph)
-bool stream_is_capturing(hipStream_t st) {
-    hipStreamCaptureStatus status = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &status) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return status != hipStreamCaptureStatusNone;
-}
 
 constexpr int LAT_TILE = npdispatch::LAT_TILE;
 static_assert(NP_KERNEL_AUTO == npdispatch::K_AUTO && NP_KERNEL_LATENCY == npdispatch::K_LATENCY && NP_KERNEL_THROUGHPUT == npdispatch::K_THROUGHPUT &&
@@ -758,10 +487,9 @@ int launch_env(np_f16_ctx *ctx, int64_t n, const np_f16_io *io, void *stream) {
     // scratch; the macro-step at n = 150 000: 29.2 -> 27.6 ms, 262 144: 45.8 -> 44.2 ms, profiles/r03f_planning_inner_pair3.log).
     if (io->cache_valid && !io->coef_cache) return fail("cache_valid set without a coef_cache buffer");
     const bool cached = STEP && io->coef_cache && io->cache_valid;
-    const bool timed = STEP && ctx->timing && !stream_is_capturing(st);  // event-attached dispatches cannot be captured into a graph
     EventLease lease(ctx);
-    if (timed && ctx->events.size() >= MAX_PENDING_EVENTS && resolve_events(ctx)) return 1;  // a caller that never polls
-    if (timed) NP_HIP(lease.take());
+    if (lease.begin(STEP, st)) return 1;
+    const bool timed = lease.timed;
     const std::pair<hipEvent_t, hipEvent_t> &ev = lease.ev;
     // the kernels live in one translation unit per task x solver x GEMM (np_env_t*s*.hip, np_env_gemm_t*s*.hip; np_env_launch.h); a reset has no
     // solver: Euler unit
@@ -776,63 +504,10 @@ int launch_env(np_f16_ctx *ctx, int64_t n, const np_f16_io *io, void *stream) {
     if (ctx->task < 0 || ctx->task > 2 || solver < 0 || solver > 1) return fail("bad task/solver");
     table[ctx->gemm_order ? 1 : 0][ctx->task][solver](l);
     NP_HIP(hipGetLastError());
-    if (timed) lease.commit();
+    lease.commit();
     return 0;
 }
 
-
-PidDev make_pid(const np_pid_gains &g, double dt) {
-    PidDev p;
-    p.Kp = (float)g.Kp;
-    p.Ki = (float)g.Ki;
-    p.Kd = (float)g.Kd;
-    p.Kff = (float)g.Kff;
-    p.Kimax = (float)g.Kimax;
-    p.tau = (float)(g.tau < 0.05 ? 0.05 : g.tau);  // rollController.py:44-45
-    p.rmax_pos = (float)g.rmax_pos;
-    p.rmax_neg = (float)g.rmax_neg;
-    p.ki_on = (g.Ki != 0.0 && dt > 0.0) ? 1 : 0;
-    return p;
-}
-
-CombatDevCfg make_combat_devcfg(const np_f16_combat_cfg &c) {
-    CombatDevCfg d;
-    d.af = make_airframe(c.airframe);
-    d.dt = (float)c.dt - 0.0f;
-    d.dt_pid = (float)c.dt;
-    d.airspeed = (float)c.airspeed;
-    d.altitude_limit = (float)c.altitude_limit;
-    d.acceleration_limit = (float)c.acceleration_limit;
-    d.max_velocity = (float)c.max_velocity;
-    d.min_velocity = (float)c.min_velocity;
-    d.min_alpha = (float)c.min_alpha;
-    d.max_alpha = (float)c.max_alpha;
-    d.min_beta = (float)c.min_beta;
-    d.max_beta = (float)c.max_beta;
-    d.dist_limit_sq = (float)(c.distance_limit * c.distance_limit);  // `self.distance_limit ** 2` is Python arithmetic
-    d.max_steps = c.max_steps;
-    d.init_T = (float)c.init_T;
-    d.alt_span = (float)(c.max_altitude - c.min_altitude);
-    d.min_altitude = (float)c.min_altitude;
-    d.vt_span = (float)(c.max_vt - c.min_vt);
-    d.min_vt = (float)c.min_vt;
-    d.yaw_span = (float)(c.max_heading - c.min_heading);
-    d.min_heading = (float)c.min_heading;
-    d.npos_span = (float)(c.max_npos - c.min_npos);
-    d.min_npos = (float)c.min_npos;
-    d.epos_span = (float)(c.max_epos - c.min_epos);
-    d.min_epos = (float)c.min_epos;
-    d.roll = make_pid(c.roll, c.dt);
-    d.pitch = make_pid(c.pitch, c.dt);
-    d.yaw = make_pid(c.yaw, c.dt);
-    d.roll_ff = (float)c.roll_ff;
-    d.gravity = (float)c.gravity;
-    d.scale_min = (float)std::min(0.5, 1000.0 / (2.0 * c.airspeed_max));   // controller.py:36-37
-    d.scale_max = (float)std::max(2.0, 1000.0 / (0.7 * c.airspeed_min));
-    d.inner_steps = c.inner_steps;
-    d.aero_1d_tables = c.aero_1d_tables ? 1 : 0;
-    return d;
-}
 
 template <bool STEP>
 int launch_combat(np_f16_ctx *ctx, int64_t num_envs, const np_f16_combat_io *io, void *stream) {
@@ -876,11 +551,10 @@ int launch_combat(np_f16_ctx *ctx, int64_t num_envs, const np_f16_combat_io *io,
     const dim3 grid((unsigned)(dual ? (n + COMBAT_DUAL_TILE - 1) / COMBAT_DUAL_TILE : latency ? (n + LAT_TILE - 1) / LAT_TILE : (n + COMBAT_BLOCK - 1) / COMBAT_BLOCK)),
         block(latency ? LAT_TILE * 4 : COMBAT_BLOCK);
     hipStream_t st = (hipStream_t)stream;
-    const bool timed = STEP && ctx->timing && !stream_is_capturing(st);
     const unsigned lds_pad = 0;
     EventLease lease(ctx);
-    if (timed && ctx->events.size() >= MAX_PENDING_EVENTS && resolve_events(ctx)) return 1;  // a caller that never polls
-    if (timed) NP_HIP(lease.take());
+    if (lease.begin(STEP, st)) return 1;
+    const bool timed = lease.timed;
     const std::pair<hipEvent_t, hipEvent_t> &ev = lease.ev;
     // pair variant (Euler, MLP numerics): the default above the latency variant's range; NP_KERNEL_THROUGHPUT pins the single-set kernel
     const bool pair = STEP && !latency && ctx->solver == 0 && !ctx->ccfg.aero_1d_tables && ctx->variant != NP_KERNEL_THROUGHPUT;
@@ -896,7 +570,7 @@ int launch_combat(np_f16_ctx *ctx, int64_t num_envs, const np_f16_combat_io *io,
     else if (STEP && ctx->solver == 1) NP_DISPATCH(a, f16_combat_kernel<1, STEP>);
     else NP_DISPATCH(a, f16_combat_kernel<0, STEP>);
     NP_HIP(hipGetLastError());
-    if (timed) lease.commit();
+    lease.commit();
     return 0;
 }
 
@@ -910,40 +584,25 @@ void np_f16_airframe_default(np_f16_airframe *out) {
     if (out) *out = airframe_defaults();
 }
 
-static int dispatch_plan_impl(int64_t n, int32_t num_cus, int32_t step, int32_t solver, int32_t tables, int32_t gemm, int32_t variant, np_dispatch_info *out);
+// the plan itself, the packer and the airframe defaults: np_f16_host.h
 int np_dispatch_plan(int64_t n, int32_t num_cus, int32_t step, int32_t solver, int32_t tables, int32_t variant, np_dispatch_info *out) {
-    return dispatch_plan_impl(n, num_cus, step, solver, tables, 0, variant, out);
+    const char *e = dispatch_plan(n, num_cus, step, solver, tables, 0, variant, BLOCK, out);
+    return e ? fail(e) : 0;
 }
 int np_dispatch_plan_gemm(int64_t n, int32_t num_cus, int32_t step, int32_t solver, int32_t variant, np_dispatch_info *out) {
     if (variant == NP_KERNEL_PAIR) return fail("np_dispatch_plan_gemm: aero_gemm_order has no pair family (NP_KERNEL_PAIR)");
-    return dispatch_plan_impl(n, num_cus, step, solver, 0, 1, variant, out);
-}
-static int dispatch_plan_impl(int64_t n, int32_t num_cus, int32_t step, int32_t solver, int32_t tables, int32_t gemm, int32_t variant, np_dispatch_info *out) {
-    if (!out) return fail("null argument");
-    if (n <= 0 || num_cus <= 0) return fail("np_dispatch_plan: n and num_cus must be positive");
-    if (variant < NP_KERNEL_AUTO || variant > NP_KERNEL_DUAL4) return fail("np_dispatch_plan: unknown variant");
-    const bool dual_pin = variant == NP_KERNEL_DUAL8 || variant == NP_KERNEL_DUAL4;   // SingleCombat only: the env kernels keep their size rule
-    const npdispatch::EnvChoice c = npdispatch::env_choice(n, num_cus, step != 0, solver, tables != 0, dual_pin ? NP_KERNEL_AUTO : variant, NP_KERNEL_AUTO, 0, BLOCK, gemm != 0);
-    const npdispatch::Limits l = npdispatch::limits_for(num_cus);
-    out->pair = c.pair; out->pair3 = c.pair3; out->latency = c.latency; out->latency8 = c.latency8; out->latency2 = c.latency2;
-    out->latency4w = c.latency4w; out->block = c.block; out->grid = c.grid;
-    out->planning_groups = npdispatch::planning_groups(n, num_cus);
-    out->actor_tile32 = npdispatch::actor_tile32(n, num_cus) ? 1 : 0;
-    const int dual = !(step && solver == 0 && !tables) ? 0 : dual_pin ? (variant == NP_KERNEL_DUAL8 ? 8 : 4)
-                     : variant == NP_KERNEL_AUTO ? npdispatch::combat_dual_waves(n, num_cus) : 0;
-    out->combat_latency = dual == 8 ? 2 : dual == 4 ? 3 : n <= l.combat_lat_max_n ? 1 : 0;
-    out->planning_mode = gemm ? (int)npdispatch::PL_LAUNCHES : npdispatch::planning_mode(n, num_cus);   // one eight-wave workgroup per CU
-    out->planning_mode_i8 = gemm ? (int)npdispatch::PL_LAUNCHES : npdispatch::planning_mode(n, num_cus, true);
-    return 0;
+    const char *e = dispatch_plan(n, num_cus, step, solver, 0, 1, variant, BLOCK, out);
+    return e ? fail(e) : 0;
 }
 int64_t np_f16_pack_kblob_gemm(const void *weights_blob, size_t nbytes, float *out, int64_t cap) {
-    std::vector<float> kb, kbd, pwl, pwl_unnorm, kbg;
-    if (pack_kblob(weights_blob, nbytes, kb, kbd, pwl, pwl_unnorm, &kbg)) return -1;
+    PackedWeights pw;
+    std::string err;
+    if (!pack_kblob(weights_blob, nbytes, pw, err)) return fail(err), -1;
     if (out) {
-        if (cap < (int64_t)kbg.size()) return fail("np_f16_pack_kblob_gemm: output buffer too small") ? -1 : -1;
-        std::memcpy(out, kbg.data(), kbg.size() * sizeof(float));
+        if (cap < (int64_t)pw.kbg.size()) return fail("np_f16_pack_kblob_gemm: output buffer too small"), -1;
+        std::memcpy(out, pw.kbg.data(), pw.kbg.size() * sizeof(float));
     }
-    return (int64_t)kbg.size();
+    return (int64_t)pw.kbg.size();
 }
 int64_t np_f16_cache_floats(int64_t n) { return n <= 0 ? 0 : ((n + BLOCK - 1) / BLOCK) * (int64_t)BLOCK * NUM_CACHE_ROWS; }
 const char *np_last_error(void) { return g_err.c_str(); }
@@ -952,8 +611,10 @@ int np_internal_fail(const char *msg) { return fail(msg ? msg : "unknown error")
 extern "C" {
 
 static int ctx_create_common(const void *weights_blob, size_t nbytes, int tables, int device, np_f16_ctx **out, bool gemm = false) {
-    std::vector<float> kb, kbd, pwl, pwl_unnorm, kbg;
-    if (pack_kblob(weights_blob, nbytes, kb, kbd, pwl, pwl_unnorm, gemm ? &kbg : nullptr)) return 1;
+    PackedWeights pw;
+    std::string err;
+    if (!pack_kblob(weights_blob, nbytes, pw, err)) return fail(err);
+    const std::vector<float> &kb = pw.kb, &kbd = pw.kbd, &kbg = pw.kbg, &pwl = pw.pwl, &pwl_unnorm = pw.pwl_unnorm;
     if (tables && pwl.empty()) return fail("cfg.aero_1d_tables needs a version-2 weights blob (PWL section)");
     int ndev = 0;
     NP_HIP(hipGetDeviceCount(&ndev));
@@ -999,21 +660,10 @@ static int ctx_create_common(const void *weights_blob, size_t nbytes, int tables
     }
     np_f16_ctx *ctx = new np_f16_ctx();
     ctx->device = device;
-    ctx->task = 0;
-    ctx->solver = 0;
-    ctx->combat = false;
-    ctx->variant = NP_KERNEL_AUTO;
     ctx->d_reset_coef = d_rc;
     ctx->d_weights = d_w;
     ctx->wt = wt;
     ctx->gemm_order = gemm;
-    ctx->timing = false;
-    ctx->t_sum_ms = 0.0;
-    ctx->t_count = 0;
-    ctx->trace = nullptr;
-    ctx->trace_cap = 0;
-    ctx->d_queue = nullptr;
-    ctx->queue_cap = 0;
     ctx->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     *out = ctx;
     return 0;

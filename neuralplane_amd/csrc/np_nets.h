@@ -20,7 +20,7 @@
 //                              output layer: (bias, 0), W[0][0..in) padded to even — its two interleaved
 //                              partial chains start from that pair (numerics spec);
 //                              then out_std, out_mean, zero padding to whole weight-stream groups
-// np_pack_kblob (np_f16_kernels.hip) also verifies that every net of a class has the fp32
+// pack_kblob (np_f16_host.h) also verifies that every net of a class has the fp32
 // normalisation constants of the class, so this static grouping cannot silently disagree with the
 // data.
 #pragma once
@@ -190,7 +190,7 @@ constexpr int KBLOB_FLOATS = class_base(NUM_CLASSES) + 2 * ASM_GROUP;
 //   output layer (in -> 1):        (W[0][0], bias), W[0][1 .. in), padded to even   [two interleaved partial chains as before:
 //                                  lo = bias + even inputs, hi = 0 + odd inputs, y = lo + hi]
 //   out_std, out_mean, zero padding to whole weight-stream groups.
-// Same values (same 2^-ACT_SHIFT scaling) as the first layout, no header; np_pack_kblob derives it from the first.
+// Same values (same 2^-ACT_SHIFT scaling) as the first layout, no header; pack_kblob places every parameter in all three.
 constexpr int dual_record_len(int n_in, int h1, int h2, int h3) {
     int n = pad2(h1 * (n_in + 1)) + pad2(h2 * (h1 + 1));
     if (h3 > 0) n += pad2(h3 * (h2 + 1)) + pad2(h3 + 1);
@@ -212,7 +212,7 @@ constexpr int KBLOB_DUAL_FLOATS = dual_class_base(NUM_CLASSES) + 2 * ASM_GROUP;
 //   output layer (in -> 1):        W[0][0..in) (+pad to even), then (bias, 0) — ONE chain, not the spec's two half-chains
 //   out_std, out_mean, zero padding to whole weight-stream groups.
 // A permutation of the first layout's record (same values, same 2^-ACT_SHIFT scaling, same length), behind the same header: class bases,
-// phase starts and the normalisation constants sit where they sit in the KBLOB.  np_pack_kblob derives it from the first.
+// phase starts and the normalisation constants sit where they sit in the KBLOB (np_f16_host.h::RECORD_LAYOUTS).
 constexpr int gemm_record_len(int n_in, int h1, int h2, int h3) {
     int n = n_in * pad2(h1) + pad2(h1) + h1 * pad2(h2) + pad2(h2);
     if (h3 > 0) n += h2 * pad2(h3) + pad2(h3) + pad2(h3) + 2;

@@ -54,7 +54,7 @@ typedef struct {
     const float *pwl; /* NULL, or t[64], a[64], x0[64], c[64] (blob PWL section) */
 } net_t;
 
-/* The airframe as data (f16o_airframe; device twin: csrc/np_f16_device.h::Airframe, built by np_f16_kernels.hip::make_airframe): the
+/* The airframe as data (f16o_airframe; device twin: csrc/np_f16_types.h::Airframe, built by np_f16_host.h::make_airframe): the
  * reference's literals (F16_dynamics.py:22-35,61-76,114-116; F16_model.py:52-62) rounded to fp32 where the literal expressions round —
  * derived constants folded in double first.  r_* = RN(1 / x) of a divisor. */
 typedef struct af_t {
