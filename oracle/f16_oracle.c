@@ -445,8 +445,8 @@ void f16o_rng_uniforms(uint64_t seed, uint64_t call_idx, int64_t row, float u8[8
  * top 21 bits of two words, pairs 8..10 are assembled from the low 11 bits of the 16 words (all 512 bits are independent).
  *   u  = (K1 + 0.5) * 2^-21                          in (0, 1): radius^2 = -2 ln u, at most 5.5 sigma
  *   th = ((K2 & 0x3FFFF) + 0.5) * (pi/4) * 2^-18     in (0, pi/4); bits 18, 19, 20 of K2: swap sin/cos, sign of cos, sign of sin
- * -2 ln u, sqrt and sin/cos are explicit fp32 sequences (fma polynomials, ~1e-7 relative) so that host and device agree bit for
- * bit; z = (sqrt(w) * noise_scale) * (cos, sin) is added to the observation with one fma. */
+ * -2 ln u, sqrt and sin/cos are explicit fp32 sequences (fma polynomials; over all 2^21 indices against fp64: radius <= 8.8e-7 relative, direction
+ * <= 7.9e-8 absolute, tests/test_noise_spec_cpu.py) so that host and device agree bit for bit; z = (sqrt(w) * noise_scale) * (cos, sin) is added to the observation with one fma. */
 static inline uint32_t f2u(float x) {
     uint32_t b;
     memcpy(&b, &x, 4);
@@ -501,10 +501,8 @@ static void unit_vector_spec(uint32_t k2, float *cs, float *sn) { /* k2: 21 bits
     *sn = (k2 & 0x100000u) ? -b : b;
 }
 
-/* 22 index pairs (K1, K2) of one row: four Philox blocks -> 11 x (21 + 21) bits */
-static void noise_indices(uint64_t seed, uint64_t call_idx, int64_t row, uint32_t k1[11], uint32_t k2[11]) {
-    uint32_t w[16];
-    for (uint32_t b = 0; b < 4; b++) rng_block(seed, call_idx, row, 2 + b, w + 4 * b);
+/* the bit assembly of the 11 index pairs from the 16 words of the four Philox blocks (exported: tests flip every input bit) */
+void f16o_noise_indices_from_words(const uint32_t w[16], uint32_t k1[11], uint32_t k2[11]) {
     for (int i = 0; i < 8; i++) {
         k1[i] = w[2 * i] >> 11;
         k2[i] = w[2 * i + 1] >> 11;
@@ -515,12 +513,23 @@ static void noise_indices(uint64_t seed, uint64_t call_idx, int64_t row, uint32_
     }
 }
 
+/* 22 index pairs (K1, K2) of one row: four Philox blocks -> 11 x (21 + 21) bits */
+static void noise_indices(uint64_t seed, uint64_t call_idx, int64_t row, uint32_t k1[11], uint32_t k2[11]) {
+    uint32_t w[16];
+    for (uint32_t b = 0; b < 4; b++) rng_block(seed, call_idx, row, 2 + b, w + 4 * b);
+    f16o_noise_indices_from_words(w, k1, k2);
+}
+
+static inline float noise_u(uint32_t k1) { /* (K1 + 0.5) * 2^-21, exact */
+    return fmaf((float)k1, 4.76837158203125e-07f, 2.384185791015625e-07f);
+}
+
 /* o[2i], o[2i+1] += (sqrt(-2 ln u_i) * scale) * (cos, sin)(direction_i), one fma each */
 static void add_rng_noise(uint64_t seed, uint64_t call_idx, int64_t row, float scale, float o[F16O_NOBS]) {
     uint32_t k1[11], k2[11];
     noise_indices(seed, call_idx, row, k1, k2);
     for (int i = 0; i < 11; i++) {
-        const float u = fmaf((float)k1[i], 4.76837158203125e-07f, 2.384185791015625e-07f); /* (K1 + 0.5) * 2^-21, exact */
+        const float u = noise_u(k1[i]);
         const float rs = sqrt_spec(neg2ln_spec(u)) * scale;
         float cs, sn;
         unit_vector_spec(k2[i], &cs, &sn);
@@ -532,6 +541,34 @@ static void add_rng_noise(uint64_t seed, uint64_t call_idx, int64_t row, float s
 void f16o_rng_normals(uint64_t seed, uint64_t call_idx, int64_t row, float z22[F16O_NOBS]) {
     for (int k = 0; k < F16O_NOBS; k++) z22[k] = 0.0f;
     add_rng_noise(seed, call_idx, row, 1.0f, z22);
+}
+
+/* Array-valued views of the generator's pieces for exhaustive tests (the index space is 2^21): the same static functions the
+ * stream above goes through, nothing restated.  Any output pointer may be NULL. */
+void f16o_noise_radius(const uint32_t *k1, int64_t n, float *u_out, float *w_out, float *r_out) {
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < n; i++) {
+        const float u = noise_u(k1[i]);
+        const float w = neg2ln_spec(u);
+        if (u_out) u_out[i] = u;
+        if (w_out) w_out[i] = w;
+        if (r_out) r_out[i] = sqrt_spec(w);
+    }
+}
+
+void f16o_noise_direction(const uint32_t *k2, int64_t n, float *cs, float *sn) {
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < n; i++) unit_vector_spec(k2[i], cs + i, sn + i);
+}
+
+void f16o_noise_indices_rows(uint64_t seed, uint64_t call_idx, int64_t row0, int64_t n, uint32_t *k1, uint32_t *k2) {
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < n; i++) noise_indices(seed, call_idx, row0 + i, k1 + 11 * i, k2 + 11 * i);
+}
+
+void f16o_rng_normals_rows(uint64_t seed, uint64_t call_idx, int64_t row0, int64_t n, float *z) {
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < n; i++) f16o_rng_normals(seed, call_idx, row0 + i, z + F16O_NOBS * i);
 }
 
 /* ------------------------------------------------------------------------------------------ */

@@ -95,6 +95,16 @@ void f16o_philox4x32(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[
 /* reset uniforms u[8] and 22 standard normals for (seed, call_idx, global_row) */
 void f16o_rng_uniforms(uint64_t seed, uint64_t call_idx, int64_t row, float u8[8]);
 void f16o_rng_normals(uint64_t seed, uint64_t call_idx, int64_t row, float z22[F16O_NOBS]);
+/* The observation-noise generator piece by piece, array-valued, for exhaustive tests over the 2^21 index
+ * values; every one calls the same static functions as f16o_rng_normals.  Output pointers may be NULL.
+ *   radius: u = (K1 + 1/2) 2^-21, w = -2 ln u, r = sqrt(w);  direction: (cos, sin) of the 21-bit K2;
+ *   indices_from_words: the 11 (K1, K2) of one row from the 16 words of Philox blocks 2..5;
+ *   *_rows: k1 / k2 [n][11], z [n][22] for global rows row0 .. row0 + n - 1 */
+void f16o_noise_radius(const uint32_t *k1, int64_t n, float *u_out, float *w_out, float *r_out);
+void f16o_noise_direction(const uint32_t *k2, int64_t n, float *cs, float *sn);
+void f16o_noise_indices_from_words(const uint32_t w16[16], uint32_t k1_11[11], uint32_t k2_11[11]);
+void f16o_noise_indices_rows(uint64_t seed, uint64_t call_idx, int64_t row0, int64_t n, uint32_t *k1, uint32_t *k2);
+void f16o_rng_normals_rows(uint64_t seed, uint64_t call_idx, int64_t row0, int64_t n, float *z);
 
 /*
  * One BaseEnv.reset() (env_base.py:83-97).

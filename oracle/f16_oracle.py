@@ -510,6 +510,62 @@ class PolicyOracle:
 
 
 # ---------------------------------------------------------------------------------------------
+# The observation-noise generator piece by piece (f16_oracle.c): no model needed
+# ---------------------------------------------------------------------------------------------
+def _u32(a):
+    return np.ascontiguousarray(a, dtype=np.uint32)
+
+
+_NOISE_LIB = None
+
+
+def _noise_lib():
+    """The library handle of the functions below, loaded once (the exhaustive tests call them thousands of times)."""
+    global _NOISE_LIB
+    if _NOISE_LIB is None:
+        _NOISE_LIB = C.CDLL(build())
+    return _NOISE_LIB
+
+
+def noise_radius(k1):
+    """21-bit radius indices -> (u, w, r) float32: u = (K1 + 1/2) 2^-21, w = neg2ln_spec(u), r = sqrt_spec(w)."""
+    k = _u32(k1).reshape(-1)
+    u, w, r = (np.empty(k.size, np.float32) for _ in range(3))
+    _noise_lib().f16o_noise_radius(_p(k, C.c_uint32), C.c_int64(k.size), _p(u), _p(w), _p(r))
+    return u, w, r
+
+
+def noise_direction(k2):
+    """21-bit direction indices -> (cs, sn) float32 of unit_vector_spec."""
+    k = _u32(k2).reshape(-1)
+    cs, sn = np.empty(k.size, np.float32), np.empty(k.size, np.float32)
+    _noise_lib().f16o_noise_direction(_p(k, C.c_uint32), C.c_int64(k.size), _p(cs), _p(sn))
+    return cs, sn
+
+
+def noise_indices_from_words(w16):
+    """The 16 words of Philox blocks 2..5 of one row -> (k1[11], k2[11]) uint32."""
+    w = _u32(w16).reshape(16)
+    k1, k2 = np.empty(11, np.uint32), np.empty(11, np.uint32)
+    _noise_lib().f16o_noise_indices_from_words(_p(w, C.c_uint32), _p(k1, C.c_uint32), _p(k2, C.c_uint32))
+    return k1, k2
+
+
+def noise_indices_rows(seed, call_idx, row0, n):
+    """(k1[n, 11], k2[n, 11]) uint32 of global rows row0 .. row0 + n - 1."""
+    k1, k2 = np.empty((n, 11), np.uint32), np.empty((n, 11), np.uint32)
+    _noise_lib().f16o_noise_indices_rows(C.c_uint64(seed), C.c_uint64(call_idx), C.c_int64(row0), C.c_int64(n), _p(k1, C.c_uint32), _p(k2, C.c_uint32))
+    return k1, k2
+
+
+def rng_normals_rows(seed, call_idx, row0, n):
+    """z[n, 22] float32: Oracle.rng_normals for global rows row0 .. row0 + n - 1."""
+    z = np.empty((n, 22), np.float32)
+    _noise_lib().f16o_rng_normals_rows(C.c_uint64(seed), C.c_uint64(call_idx), C.c_int64(row0), C.c_int64(n), _p(z))
+    return z
+
+
+# ---------------------------------------------------------------------------------------------
 # Rollout storage: ReplayBuffer.compute_returns (f16_rollout.inc)
 # ---------------------------------------------------------------------------------------------
 def rollout_returns(rewards, value_preds, masks, bad_masks, next_value, gamma, gae_lambda, use_gae, proper):

@@ -265,12 +265,17 @@ def test_constant_division_sequence_equals_ieee_division_on_this_device_for_all_
         total_soft += cnt[1]
         rows.append({'c': c, 'mismatch_normal_range': int(cnt[0]), 'mismatch_tiny_or_denormal': int(cnt[1]), 'inputs': int(cnt[2])})
         assert cnt[1] < 2 ** 32 // 50, (c, cnt[1])     # only sub-2^-100 inputs / denormal quotients (< 2 % of all bit patterns)
+    _write_report('divc_selfcheck.json', rows)
+
+
+def _write_report(name, obj):
+    """A test's report as JSON in the repository's report directory (shared with tests/test_gpu_noise_edges.py); a read-only tree is fine."""
     import json
     import os
     out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'gpurun_out')
     try:
         os.makedirs(out, exist_ok=True)
-        json.dump(rows, open(os.path.join(out, 'divc_selfcheck.json'), 'w'), indent=1)
+        json.dump(obj, open(os.path.join(out, name), 'w'), indent=1)
     except OSError:
         pass
 
