@@ -509,6 +509,20 @@ int np_f16_get_timing_samples(np_f16_ctx *ctx, float *ms_out, int64_t capacity, 
  * (2^32).  Blocking; about 10 ms per constant. */
 int np_selfcheck_divc(float c, uint64_t *counts3, int device);
 
+/* Self-check of the numerics spec on the device at hand (test infrastructure, like np_selfcheck_divc): ONE elementary function of the spec
+ * (csrc/np_math.h, csrc/np_actor.h: the functions the production kernels inline, not copies) applied to every row of a host array.
+ * in [n][in_cols] and out [n][out_cols] are HOST pointers, row-major; the call allocates, copies in, launches one kernel (one row per
+ * thread), copies back and frees.  Inputs -> outputs per function id:
+ *   SINCOS x -> sin, cos;  SINCOSTAN x -> sin, cos, tan;  POW x, y -> x^y;  POW_POSEXP x -> x^param (param positive and finite);
+ *   ACOS, ATANH, EXP, WRAP_PI, ACT_EXP, ACT_SIGMOID, ACT_TANH x -> f(x);  NORM3 a, b, c -> |(a, b, c)|;  DOT3 a0, a1, a2, b0, b1, b2 -> a . b.
+ * Fails (np_last_error) on an unknown id, column counts other than the function's, null pointers and n outside [0, 2^24].  The tests
+ * compare the outputs bit for bit with a scalar CPU restatement of the same sequences (same ids).  Blocking. */
+enum {
+    NP_MATH_SINCOS = 0, NP_MATH_SINCOSTAN = 1, NP_MATH_POW = 2, NP_MATH_POW_POSEXP = 3, NP_MATH_ACOS = 4, NP_MATH_ATANH = 5, NP_MATH_EXP = 6,
+    NP_MATH_NORM3 = 7, NP_MATH_DOT3 = 8, NP_MATH_WRAP_PI = 9, NP_MATH_ACT_EXP = 10, NP_MATH_ACT_SIGMOID = 11, NP_MATH_ACT_TANH = 12, NP_MATH_NUM_FN = 13
+};
+int np_selfcheck_math(int32_t fn, int64_t n, const float *in, int32_t in_cols, double param, float *out, int32_t out_cols, int device);
+
 /* Profiling hook: while a device buffer of capacity_workgroups x NP_TRACE_WORDS uint64 is set (NULL clears), every
  * np_f16_step launch on this context writes one record per workgroup: [0] shader-clock counter at entry, [1] after the
  * de-phasing delay, [2] at exit, [3] / [4] the constant-rate (100 MHz) counter at entry / exit, [5] XCC id << 32 | HW_ID.

@@ -235,6 +235,34 @@ __global__ __launch_bounds__(256) void divc_sweep_kernel(float c, float rc, unsi
     }
 }
 
+// Self-check of the numerics spec's elementary functions on THIS device: row i of in[n][in_cols] through ONE function of np_math.h /
+// np_actor.h — the very functions the production kernels inline, no copies — into out[n][out_cols] (ids and column counts:
+// NP_MATH_* in include/neuralplane_amd.h; `param` is np_pow_posexp's exponent).  The tests hold every output bit to the oracle's
+// scalar restatement.  One row per thread; fn is uniform, so the switch does not diverge.
+__global__ __launch_bounds__(256) void math_selfcheck_kernel(int fn, long long n, const float *__restrict__ in, int in_cols, double param,
+                                                             float *__restrict__ out, int out_cols) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float *x = in + i * in_cols;
+    float *o = out + i * out_cols;
+    switch (fn) {
+    case NP_MATH_SINCOS: np_sincos(x[0], o[0], o[1]); break;
+    case NP_MATH_SINCOSTAN: np_sincostan(x[0], o[0], o[1], o[2]); break;
+    case NP_MATH_POW: o[0] = np_pow(x[0], x[1]); break;
+    case NP_MATH_POW_POSEXP: o[0] = np_pow_posexp(x[0], param); break;
+    case NP_MATH_ACOS: o[0] = np_acos(x[0]); break;
+    case NP_MATH_ATANH: o[0] = np_atanh(x[0]); break;
+    case NP_MATH_EXP: o[0] = np_exp(x[0]); break;
+    case NP_MATH_NORM3: o[0] = np_norm3(x[0], x[1], x[2]); break;
+    case NP_MATH_DOT3: o[0] = np_dot3(x[0], x[1], x[2], x[3], x[4], x[5]); break;
+    case NP_MATH_WRAP_PI: o[0] = np_wrap_pi(x[0]); break;
+    case NP_MATH_ACT_EXP: o[0] = npact::act_exp(x[0]); break;
+    case NP_MATH_ACT_SIGMOID: o[0] = npact::act_sigmoid(x[0]); break;
+    case NP_MATH_ACT_TANH: o[0] = npact::act_tanh(x[0]); break;
+    default: break;
+    }
+}
+
 }  // namespace npf16
 
 // =================================================================================================
@@ -1482,6 +1510,40 @@ int np_selfcheck_divc(float c, uint64_t *counts3, int device) {
     (void)hipFree(d);
     NP_HIP(e);
     for (int k = 0; k < 3; k++) counts3[k] = h[k];
+    return 0;
+}
+
+int np_selfcheck_math(int32_t fn, int64_t n, const float *in, int32_t in_cols, double param, float *out, int32_t out_cols, int device) {
+    static const int8_t cols[NP_MATH_NUM_FN][2] = {{1, 2}, {1, 3}, {2, 1}, {1, 1}, {1, 1}, {1, 1}, {1, 1}, {3, 1}, {6, 1}, {1, 1}, {1, 1}, {1, 1}, {1, 1}};
+    if (fn < 0 || fn >= NP_MATH_NUM_FN) return fail("np_selfcheck_math: unknown function id (NP_MATH_*)");
+    if (!in || !out) return fail("np_selfcheck_math: null argument");
+    if (in_cols != cols[fn][0] || out_cols != cols[fn][1])
+        return fail("np_selfcheck_math: function " + std::to_string(fn) + " takes " + std::to_string(cols[fn][0]) + " input and " + std::to_string(cols[fn][1]) +
+                    " output columns");
+    if (n < 0 || n > (1ll << 24)) return fail("np_selfcheck_math: n must be in [0, 2^24]");
+    if (fn == NP_MATH_POW_POSEXP && !(param > 0.0 && std::isfinite(param)))
+        return fail("np_selfcheck_math: NP_MATH_POW_POSEXP needs a positive finite exponent in param (np_pow_posexp's contract)");
+    int ndev = 0;
+    NP_HIP(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev) return fail("no such HIP device (this library has no CPU fallback)");
+    if (n == 0) return 0;
+    DeviceGuard guard;
+    NP_HIP(guard.enter(device));
+    const size_t in_bytes = (size_t)n * in_cols * sizeof(float), out_bytes = (size_t)n * out_cols * sizeof(float);
+    float *d_in = nullptr, *d_out = nullptr;
+    NP_HIP(hipMalloc(&d_in, in_bytes));
+    hipError_t e = hipMalloc(&d_out, out_bytes);
+    if (e == hipSuccess) e = hipMemcpy(d_in, in, in_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(d_out, 0xFF, out_bytes);   // a row the kernel skipped reads back as NaN, not as a plausible zero
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(npf16::math_selfcheck_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, (int)fn, (long long)n, d_in, (int)in_cols, param, d_out,
+                           (int)out_cols);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(out, d_out, out_bytes, hipMemcpyDeviceToHost);
+    (void)hipFree(d_in);
+    if (d_out) (void)hipFree(d_out);
+    NP_HIP(e);
     return 0;
 }
 

@@ -1173,3 +1173,46 @@ int f16o_num_threads(void) {
 #include "f16_actor.inc"
 #include "f16_actor_i8.inc"
 #include "f16_rollout.inc"
+
+/* ------------------------------------------------------------------------------------------ */
+/* The elementary functions of the numerics spec, batched: row i of in[n][in_cols] through ONE */
+/* of the scalar functions above into out[n][out_cols] (device twin: np_selfcheck_math in      */
+/* include/neuralplane_amd.h, same ids and column counts).  Returns non-zero on an unknown id  */
+/* or a column count that is not the function's.                                               */
+/* ------------------------------------------------------------------------------------------ */
+/* csrc/np_math.h::np_pow_posexp: x^y for an exponent known to be positive and finite, handed over as the double the sequence works in
+ * (the kernels' atmosphere model; f16o_pow(x, (float)y) gives the same bits for an exponent that is a float) */
+static float pow_posexp(float xf, double y) {
+    const double x = (double)xf;
+    if (x != x) return NAN;
+    if (x < 0.0) return NAN;
+    if (x == 0.0) return 0.0f;
+    if (x == INFINITY) return INFINITY;
+    return (float)exp2_d(y * log2_d(x));
+}
+
+int f16o_math_array(int fn, int64_t n, const float *in, int in_cols, double param, float *out, int out_cols) {
+    static const int8_t cols[F16O_MATH_NUM_FN][2] = {{1, 2}, {1, 3}, {2, 1}, {1, 1}, {1, 1}, {1, 1}, {1, 1}, {3, 1}, {6, 1}, {1, 1}, {1, 1}, {1, 1}, {1, 1}};
+    if (fn < 0 || fn >= F16O_MATH_NUM_FN || !in || !out || n < 0 || in_cols != cols[fn][0] || out_cols != cols[fn][1]) return 1;
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < n; i++) {
+        const float *x = in + i * in_cols;
+        float *o = out + i * out_cols;
+        switch (fn) {
+        case F16O_MATH_SINCOS: f16o_sincos(x[0], o + 0, o + 1); break;
+        case F16O_MATH_SINCOSTAN: f16o_sincos(x[0], o + 0, o + 1); o[2] = f16o_tan(x[0]); break;
+        case F16O_MATH_POW: o[0] = f16o_pow(x[0], x[1]); break;
+        case F16O_MATH_POW_POSEXP: o[0] = pow_posexp(x[0], param); break;
+        case F16O_MATH_ACOS: o[0] = f16o_acos(x[0]); break;
+        case F16O_MATH_ATANH: o[0] = f16o_atanh(x[0]); break;
+        case F16O_MATH_EXP: o[0] = f16o_exp(x[0]); break;
+        case F16O_MATH_NORM3: o[0] = norm3(x[0], x[1], x[2]); break;
+        case F16O_MATH_DOT3: o[0] = dot3(x[0], x[1], x[2], x[3], x[4], x[5]); break;
+        case F16O_MATH_WRAP_PI: o[0] = f16o_wrap_pi(x[0]); break;
+        case F16O_MATH_ACT_EXP: o[0] = act_exp(x[0]); break;
+        case F16O_MATH_ACT_SIGMOID: o[0] = act_sigmoid(x[0]); break;
+        default: o[0] = act_tanh(x[0]); break;
+        }
+    }
+    return 0;
+}

@@ -92,6 +92,17 @@ float f16o_tan(float x);
 float f16o_pow(float x, float y);
 float f16o_wrap_pi(float x);
 void f16o_philox4x32(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
+/* The same functions and the rest of the spec's elementary layer, batched over rows (OpenMP): fn = F16O_MATH_*, in [n][in_cols] -> out [n][out_cols]
+ *   SINCOS x -> sin, cos;  SINCOSTAN x -> sin, cos, tan;  POW x, y -> x^y;  POW_POSEXP x -> x^param (the kernels' np_pow_posexp: exponent as a double);
+ *   ACOS, ATANH, EXP, WRAP_PI x -> f(x);  NORM3 a, b, c;  DOT3 a0, a1, a2, b0, b1, b2;  ACT_EXP, ACT_SIGMOID, ACT_TANH: the controller's
+ *   fp32 nonlinearities (f16_actor.inc).  Calls the scalar functions the trajectories use; evaluated in the current mode (f16o_set_mode).
+ * Returns non-zero on an unknown id, a column count that is not the function's, or a null pointer. */
+enum {
+    F16O_MATH_SINCOS = 0, F16O_MATH_SINCOSTAN = 1, F16O_MATH_POW = 2, F16O_MATH_POW_POSEXP = 3, F16O_MATH_ACOS = 4, F16O_MATH_ATANH = 5,
+    F16O_MATH_EXP = 6, F16O_MATH_NORM3 = 7, F16O_MATH_DOT3 = 8, F16O_MATH_WRAP_PI = 9, F16O_MATH_ACT_EXP = 10, F16O_MATH_ACT_SIGMOID = 11,
+    F16O_MATH_ACT_TANH = 12, F16O_MATH_NUM_FN = 13
+};
+int f16o_math_array(int fn, int64_t n, const float *in, int in_cols, double param, float *out, int out_cols);
 /* reset uniforms u[8] and 22 standard normals for (seed, call_idx, global_row) */
 void f16o_rng_uniforms(uint64_t seed, uint64_t call_idx, int64_t row, float u8[8]);
 void f16o_rng_normals(uint64_t seed, uint64_t call_idx, int64_t row, float z22[F16O_NOBS]);

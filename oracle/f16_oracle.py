@@ -566,6 +566,33 @@ def rng_normals_rows(seed, call_idx, row0, n):
 
 
 # ---------------------------------------------------------------------------------------------
+# The elementary functions of the numerics spec, batched (f16_oracle.c::f16o_math_array): no model needed
+# ---------------------------------------------------------------------------------------------
+MATH_FN = {'SINCOS': 0, 'SINCOSTAN': 1, 'POW': 2, 'POW_POSEXP': 3, 'ACOS': 4, 'ATANH': 5, 'EXP': 6, 'NORM3': 7, 'DOT3': 8, 'WRAP_PI': 9,
+           'ACT_EXP': 10, 'ACT_SIGMOID': 11, 'ACT_TANH': 12}                      # F16O_MATH_* == NP_MATH_* of the device's self-check
+MATH_COLS = {'SINCOS': (1, 2), 'SINCOSTAN': (1, 3), 'POW': (2, 1), 'POW_POSEXP': (1, 1), 'ACOS': (1, 1), 'ATANH': (1, 1), 'EXP': (1, 1),
+             'NORM3': (3, 1), 'DOT3': (6, 1), 'WRAP_PI': (1, 1), 'ACT_EXP': (1, 1), 'ACT_SIGMOID': (1, 1), 'ACT_TANH': (1, 1)}   # (inputs, outputs) per row
+
+
+def math_array(fn, x, param=0.0):
+    """One elementary function of the spec (a MATH_FN name) over the rows of x [n, in_cols] float32 -> out [n, out_cols] float32, in the
+    shipped numerics (mode 0), OpenMP over rows.  param: the exponent of POW_POSEXP."""
+    ci, co = MATH_COLS[fn]
+    x = _f32(x).reshape(-1, ci)
+    out = np.empty((x.shape[0], co), np.float32)
+    lib = _noise_lib()
+    lib.f16o_math_array.argtypes = [C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_int]
+    mode = lib.f16o_get_mode()
+    lib.f16o_set_mode(0)
+    try:
+        rc = lib.f16o_math_array(MATH_FN[fn], x.shape[0], x.ctypes.data, ci, float(param), out.ctypes.data, co)
+    finally:
+        lib.f16o_set_mode(mode)
+    assert rc == 0, (fn, x.shape)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
 # Rollout storage: ReplayBuffer.compute_returns (f16_rollout.inc)
 # ---------------------------------------------------------------------------------------------
 def rollout_returns(rewards, value_preds, masks, bad_masks, next_value, gamma, gae_lambda, use_gae, proper):

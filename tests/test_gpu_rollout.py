@@ -34,7 +34,8 @@ def test_compute_returns_equals_the_reference_buffer(golden_dir, proper, gae):
             assert np.array_equal(batch[5].cpu().numpy(), g[f'batch{b}::returns']) and np.array_equal(batch[0].cpu().numpy(), g[f'batch{b}::obs'])
 
 
-@pytest.mark.parametrize('T,N', [(1, 1), (7, 63), (37, 1000), (128, 257), (3, 70001)])
+# N >= 500 000 columns take the 256-thread instantiations (np_rollout.h: MANY_COLUMNS): at the threshold and with a ragged last block
+@pytest.mark.parametrize('T,N', [(1, 1), (7, 63), (37, 1000), (128, 257), (3, 70001), (3, 500000), (2, 500001)])
 @pytest.mark.parametrize('mode', [(0, 0), (0, 1), (1, 0), (1, 1)])
 def test_hip_equals_oracle_on_ragged_shapes_and_hostile_values(T, N, mode):
     from neuralplane_amd import _lib
