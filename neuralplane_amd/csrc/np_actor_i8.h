@@ -106,6 +106,24 @@ __device__ __forceinline__ void quantise_store(const float (&y)[16], int ex, flo
     dst[128] = l2;
 }
 
+// max |.| as an UNSIGNED maximum of the bit patterns without their sign: for finite values the number fmaxf gives, while an infinity or a NaN
+// (which fmaxf would skip) wins over every finite value.  The row's non-finite flag (f16_actor_i8.inc::ai8_row) travels in the quantity the
+// second LayerNorm's exchange reduces anyway and stays in LDS8_PH, which nothing else writes, to the end of the call: no register is held
+// across the matrix phases (the body has none to spare).
+__device__ __forceinline__ float absmax_bits(float m, float x) {
+    const unsigned a = __float_as_uint(m), b = __float_as_uint(x) & 0x7FFFFFFFu;
+    return __uint_as_float(a > b ? a : b);
+}
+__device__ __forceinline__ float absmax8(const float4 &p0, const float4 &p1) {
+    return absmax_bits(absmax_bits(absmax_bits(p0.x, p0.y), absmax_bits(p0.z, p0.w)), absmax_bits(absmax_bits(p1.x, p1.y), absmax_bits(p1.z, p1.w)));
+}
+// a row exponent of 106 or more (|x| >= 2^105, an infinity, a NaN): beyond it the epilogue's u * 2^(ex - 17) can overflow whatever the weights
+__device__ __forceinline__ bool nonfinite(float x) { return (__float_as_uint(x) & 0x7FFFFFFFu) >= 0x74000000u; }
+__device__ __forceinline__ bool row_bad(const float *lds, int a) {
+    const float *part_h = lds + LDS8_PH;
+    return nonfinite(absmax8(*reinterpret_cast<const float4 *>(part_h + a * 8), *reinterpret_cast<const float4 *>(part_h + a * 8 + 4)));
+}
+
 // Everything below is written for T tiles of 32 aircraft per workgroup that share ONE weight stream: a fragment in registers multiplies the
 // B operands of tile 0, then of tile 1, ... (T x the class sums, 1 / T of the L2 traffic per aircraft — the stand-alone kernel at large batches
 // would be bound by exactly that traffic: 592 KB per tile and call).  T = 1 is what is instantiated: T = 2 was built, is bit-identical, and was NOT
@@ -166,7 +184,7 @@ __device__ __forceinline__ void layernorm_acc(const float (&v)[T][16], const flo
         }
         if constexpr (EXTRA) {
             const float4 p0 = *reinterpret_cast<const float4 *>(part_h + a * 8), p1 = *reinterpret_cast<const float4 *>(part_h + a * 8 + 4);
-            extra_out[t] = fmaxf(fmaxf(fmaxf(p0.x, p0.y), fmaxf(p0.z, p0.w)), fmaxf(fmaxf(p1.x, p1.y), fmaxf(p1.z, p1.w)));
+            extra_out[t] = absmax8(p0, p1);
         }
         const float mean = total * (1.0f / 128.0f);
         float q = 0.0f, m = 0.0f;
@@ -349,6 +367,7 @@ __device__ __forceinline__ void actor8_body(float *lds, float *park, const float
     // base.feature_norm over the 22 observations: every lane computes its aircraft's (no exchange), quantises, and picks the 16 k-slots of
     // its half: slot e <-> feature 8 (e >> 2) + 4 h + (e & 3); slots of features >= 22 are zero (as the packed weights are)
     i32x4 x1reg[T][3];
+    float hmax_l[T], hmax[T];
 #pragma unroll
     for (int t = 0; t < T; t++) {
         float total = 0.0f;
@@ -363,7 +382,9 @@ __device__ __forceinline__ void actor8_body(float *lds, float *park, const float
             m = fmaxf(m, fabsf(d[j]));
         }
         const float rstd = 1.0f / sqrtf(q * (1.0f / (float)NOBS) + 1e-5f);
-        ex[t] = exponent_of(fmaf(m * rstd, W[LNMAX + 0], W[LNMAX + 1]) * 1.000001f);
+        const float bound = fmaf(m * rstd, W[LNMAX + 0], W[LNMAX + 1]) * 1.000001f;
+        ex[t] = exponent_of(bound);
+        hmax_l[t] = nonfinite(bound) ? bound : 0.0f;   // a non-finite observation row joins the recurrent state's flag: the start value of its local maximum
         const float scale = pow2f(XBITS - ex[t]), magic = __uint_as_float(MAGIC_BITS);
         unsigned p[32];
 #pragma unroll
@@ -397,12 +418,10 @@ __device__ __forceinline__ void actor8_body(float *lds, float *park, const float
     // Linear(128, 128) + ReLU + LayerNorm; the recurrent state's row maximum rides in the LayerNorm's first exchange
     mblock<4, 4, T>(wf, f_gi + 4 * MB_BYTES_K4, lds, LDS8_XF, none, tab + T_SW + O_L2, tab + T_BIAS + O_L2, fbase, ex, lane, v);
     relu_acc<T>(v);
-    float hmax_l[T], hmax[T];
 #pragma unroll
     for (int t = 0; t < T; t++) {
-        hmax_l[t] = 0.0f;
 #pragma unroll
-        for (int r = 0; r < 16; r++) hmax_l[t] = fmaxf(hmax_l[t], fabsf(hm[t][r]));
+        for (int r = 0; r < 16; r++) hmax_l[t] = absmax_bits(hmax_l[t], hm[t][r]);
     }
     layernorm_acc<true, T>(v, tab + T_LN + 256, tab + T_LN + 384, W[LNMAX + 4], W[LNMAX + 5], lds, blk, a, fbase, y, ex, hmax_l, hmax);
 #pragma unroll
@@ -410,7 +429,14 @@ __device__ __forceinline__ void actor8_body(float *lds, float *park, const float
         eh[t] = exponent_of(hmax[t]);
         quantise_store(y[t], ex[t], lds + t * ACTOR8_LDS_FLOATS + LDS8_XF, w, lane);
         quantise_store(hm[t], eh[t], lds + t * ACTOR8_LDS_FLOATS + LDS8_HF, w, lane);
-        park_store(park + t * ACTOR8_PARK_FLOATS, hm[t], tid);   // (own data: no barrier of its own)
+        {
+            // a non-finite row: the parked state is NaN, so the new recurrent state (hq - n) z + n is NaN in all 128 features; x * 1 keeps every bit of a finite row
+            const float one = nonfinite(hmax[t]) ? __uint_as_float(0x7FC00000u) : 1.0f;
+            float hp[16];
+#pragma unroll
+            for (int r = 0; r < 16; r++) hp[r] = hm[t][r] * one;
+            park_store(park + t * ACTOR8_PARK_FLOATS, hp, tid);
+        }   // (own data: no barrier of its own)
     }
     __syncthreads();
     // rnn: GRU cell.  Gate order of the ARITHMETIC as in torch (r, z, n); evaluated z, r, n so that only one gate vector is in registers beside
@@ -491,6 +517,8 @@ __device__ __forceinline__ void actor8_body(float *lds, float *park, const float
         tot = tot + q0.x; tot = tot + q0.y; tot = tot + q0.z; tot = tot + q0.w;
         tot = tot + q1.x; tot = tot + q1.y; tot = tot + q1.z; tot = tot + q1.w;
         action[t] = TANH ? act_tanh(tot) : tot;
+        // a non-finite row: NaN (the flag is re-read from the exchange)
+        action[t] = row_bad(lds + t * ACTOR8_LDS_FLOATS, a) ? __uint_as_float(0x7FC00000u) : action[t];
     }
 }
 

@@ -224,6 +224,15 @@ int f16o_policy_act_i8(const float *wa, const float *wc, const float *std, const
                        const float *obs, const float *ha_in, const float *hc_in, const float *mask, const float *noise, float *values,
                        float *actions, float *log_probs, float *ha_out, float *hc_out);
 
+/* the block fixed point piece by piece (f16_actor_i8.inc; each calls the static function the forward pass uses).  Non-zero: bad argument / out of memory.
+ *   quantise   x[n_rows][n <= 128], ex[n_rows] -> q[n_rows][n] (before limb splitting), limbs[n_rows][3][n], qsum[n_rows][n] (the magic-number sum; may be 0)
+ *   layernorm  LayerNorm `which` (0: 22 wide, 1..5: 128 wide) of the packed network w -> y, ex[n_rows]; f16o_actor_layernorm: the fp32 spec's order
+ *   dense      Linear `layer` (0 L1, 1 L2, 2 GI, 3 GH, 4 A1, 5 A2): x[n_rows][n_in], ex -> y[n_rows][n_out], class sums c[n_rows][n_out][4] */
+int f16o_actor_i8_quantise(int64_t n_rows, int n, const float *x, const int32_t *ex, int32_t *q, int8_t *limbs, float *qsum);
+int f16o_actor_i8_layernorm(const float *w, int which, int64_t n_rows, const float *x, float *y, int32_t *ex);
+int f16o_actor_layernorm(const float *w, int which, int64_t n_rows, const float *x, float *y);
+int f16o_actor_i8_dense(const float *w, int layer, int64_t n_rows, const float *x, const int32_t *ex, float *y, int32_t *c);
+
 /* ReplayBuffer.compute_returns (f16_rollout.inc; reference algorithms/utils/buffer.py:139-173): rewards [T][N], value_preds / masks /
  * bad_masks / returns [T+1][N], next_value [N]; GAE modes write value_preds[T], the others returns[T] */
 void f16o_rollout_returns(int64_t T, int64_t N, double gamma, double gae_lambda, int use_gae, int proper, const float *rewards,

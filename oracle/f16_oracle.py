@@ -466,6 +466,32 @@ class ActorOracle:
         assert self.lib.f16o_actor_i8_weights(_p(self.w), C.c_int(layer), _p(wq, C.c_int32), _p(ew, C.c_int32)) == 0
         return wq, ew
 
+    LAYER_SHAPES = ((22, 128), (128, 128), (128, 384), (128, 384), (128, 128), (128, 128))     # (n_in, n_out) of L1, L2, GI, GH, A1, A2
+
+    def i8_layernorm(self, which, x):
+        """LayerNorm `which` (0: the observation's; 1..5) of the i8 restatement over the rows of x -> (y, ex int32[n])."""
+        n = 22 if which == 0 else 128
+        x = _f32(x).reshape(-1, n)
+        y, ex = np.empty_like(x), np.empty(x.shape[0], np.int32)
+        assert self.lib.f16o_actor_i8_layernorm(_p(self.w), C.c_int(which), C.c_int64(x.shape[0]), _p(x), _p(y), _p(ex, C.c_int32)) == 0
+        return y, ex
+
+    def fp32_layernorm(self, which, x):
+        """The same LayerNorm in the fp32 restatement's summation order (f16_actor.inc)."""
+        x = _f32(x).reshape(-1, 22 if which == 0 else 128)
+        y = np.empty_like(x)
+        assert self.lib.f16o_actor_layernorm(_p(self.w), C.c_int(which), C.c_int64(x.shape[0]), _p(x), _p(y)) == 0
+        return y
+
+    def i8_dense(self, layer, x, ex):
+        """Quantised Linear `layer` over the rows of x with row exponents ex -> (y[n, n_out], class sums c[n, n_out, 4] int32)."""
+        n_in, n_out = self.LAYER_SHAPES[layer]
+        x, ex = _f32(x).reshape(-1, n_in), np.ascontiguousarray(ex, np.int32).reshape(-1)
+        assert ex.size == x.shape[0]
+        y, c = np.empty((x.shape[0], n_out), np.float32), np.empty((x.shape[0], n_out, 4), np.int32)
+        assert self.lib.f16o_actor_i8_dense(_p(self.w), C.c_int(layer), C.c_int64(x.shape[0]), _p(x), _p(ex, C.c_int32), _p(y), _p(c, C.c_int32)) == 0
+        return y, c
+
     def forward(self, obs, h, masks):
         obs, h = _f32(obs), _f32(h).reshape(-1, 128)
         m = _f32(masks).reshape(-1)
@@ -507,6 +533,19 @@ class PolicyOracle:
                 _p(hc), _p(m), _p(noise), _p(values), _p(actions), _p(logp), _p(ha_out), _p(hc_out))
         assert self.numerics == 'fp32' or rc == 0
         return values, actions, logp, ha_out, hc_out
+
+
+def i8_quantise(x, ex):
+    """The block fixed point's quantiser (f16_actor_i8.inc) over the rows of x [n_rows, n <= 128] with row exponents ex ->
+    (q int32[n_rows, n] before limb splitting, limbs int8[n_rows, 3, n], qsum float32[n_rows, n]: the magic-number sum)."""
+    x = _f32(x)
+    assert x.ndim == 2 and 1 <= x.shape[1] <= 128
+    ex = np.ascontiguousarray(ex, np.int32).reshape(-1)
+    assert ex.size == x.shape[0]
+    q, limbs, qsum = np.empty(x.shape, np.int32), np.empty((x.shape[0], 3, x.shape[1]), np.int8), np.empty(x.shape, np.float32)
+    assert C.CDLL(build()).f16o_actor_i8_quantise(C.c_int64(x.shape[0]), C.c_int(x.shape[1]), _p(x), _p(ex, C.c_int32), _p(q, C.c_int32),
+                                                  _p(limbs, C.c_int8), _p(qsum)) == 0
+    return q, limbs, qsum
 
 
 # ---------------------------------------------------------------------------------------------
