@@ -465,6 +465,29 @@ enum { NP_KERNEL_AUTO = 0, NP_KERNEL_LATENCY = 1, NP_KERNEL_THROUGHPUT = 2, NP_K
        NP_KERNEL_DUAL8 = 7, NP_KERNEL_DUAL4 = 8 /* SingleCombat contexts only: eight / four waves per 128-aircraft tile (Euler, MLP numerics; otherwise the automatic rule applies) */ };
 int np_f16_set_kernel_variant(np_f16_ctx *ctx, int variant);
 
+/* Per-row airframes: a FLEET (no ABI bump: two new entry points, no struct changes).  A context created by np_f16_ctx_create may carry a table of
+ * k airframe classes (1 <= k <= 65 536) and a device array airframe_index[n] (int32): row i of every following np_f16_reset / np_f16_step /
+ * np_f16_derived / np_f16_lowlevel_obs / np_planning_targets_obs / np_planning_inner_loop flies class airframe_index[i].  Each class is an
+ * np_f16_airframe block exactly as np_f16_cfg.airframe takes it (all zero = the F-16) and is rounded exactly as that one is, so every row
+ * computes, bit for bit, what the same row computes in a one-airframe context created with its class.  Weights, scenario constants, numerics
+ * spec and the RNG stream are the context's, unchanged.
+ *   np_f16_set_fleet        validates every class (a refusal names the class number), builds the records and uploads them; k = 0 removes
+ *                           the fleet (and the index).  It synchronises the device.  cfg.airframe stays what the context was created with
+ *                           and is not read while a fleet is set.
+ *   np_f16_set_fleet_index  device_index is DEVICE memory owned by the caller, n entries, and must stay valid (and unchanged while launches
+ *                           are in flight) until it is replaced or the fleet is removed.  Every later launch must fit: a launch of more
+ *                           than n rows is refused.  Values must lie in 0 .. k-1 — the caller's contract (the Python layer checks it once,
+ *                           when the index is set); the kernels clamp an index to k-1 (unsigned) before it forms an address, so a
+ *                           bad value flies the wrong class but reads nothing outside the table.
+ * After either call the caller clears np_f16_io.cache_valid for the next step: the cross-step cache holds the atmosphere power of the
+ * class that wrote it.
+ * A context with a fleet runs the fleet kernels — the throughput shape (128-row tiles, one aircraft per lane) at every n; np_dispatch_plan does
+ * not describe them.  Refused, in words that name the fleet: SingleCombat contexts, contexts with aero_gemm_order,
+ * np_f16_set_kernel_variant with anything but NP_KERNEL_AUTO / NP_KERNEL_THROUGHPUT, and the persistent / queue / guest / dual modes of
+ * np_planning_inner_loop (NP_PLANNING_AUTO resolves to the launches).  aero_1d_tables stays allowed. */
+int np_f16_set_fleet(np_f16_ctx *ctx, const np_f16_airframe *classes, int32_t k);
+int np_f16_set_fleet_index(np_f16_ctx *ctx, const int32_t *device_index, int64_t n);
+
 /* Which variant / tiling / row grouping a launch of n rows gets on a device with num_cus compute units (ABI 14): the selection
  * np_f16_step, np_f16_combat_step, np_actor_forward and np_planning_inner_loop apply, as a pure function (no device needed, the NPF16_*
  * environment overrides not applied).  Every threshold is a number of tiles per CU or wave slots per SIMD, measured on the 256-CU device

@@ -149,7 +149,8 @@ def pack_kblob_gemm(blob):
 
 EXPORTS = ('np_abi_version', 'np_f16_airframe_default', 'np_f16_cache_floats', 'np_last_error', 'np_f16_ctx_create', 'np_f16_ctx_destroy', 'np_f16_reset',
            'np_f16_step', 'np_f16_derived', 'np_f16_aero_coefficients', 'np_f16_lowlevel_obs', 'np_f16_set_timing', 'np_f16_get_timing', 'np_f16_get_timing_samples', 'np_f16_set_trace', 'np_selfcheck_divc', 'np_selfcheck_math',
-           'np_f16_combat_ctx_create', 'np_f16_combat_reset', 'np_f16_combat_step', 'np_f16_set_kernel_variant', 'np_actor_forward', 'np_rollout_returns', 'np_planning_inner_loop', 'np_planning_check', 'np_actor_pack_i8', 'np_rollout_insert', 'np_policy_act', 'np_planning_targets_obs', 'np_dispatch_plan', 'np_dispatch_plan_gemm', 'np_f16_pack_kblob_gemm')
+           'np_f16_combat_ctx_create', 'np_f16_combat_reset', 'np_f16_combat_step', 'np_f16_set_kernel_variant', 'np_actor_forward', 'np_rollout_returns', 'np_planning_inner_loop', 'np_planning_check', 'np_actor_pack_i8', 'np_rollout_insert', 'np_policy_act', 'np_planning_targets_obs', 'np_dispatch_plan', 'np_dispatch_plan_gemm', 'np_f16_pack_kblob_gemm',
+           'np_f16_set_fleet', 'np_f16_set_fleet_index')
 KERNEL_VARIANTS = {'auto': 0, 'latency': 1, 'throughput': 2, 'pair': 3, 'latency8': 4, 'latency2': 5, 'latency4w': 6, 'dual8': 7, 'dual4': 8}
 
 _lib = None
@@ -193,6 +194,9 @@ def load():
     lib.np_planning_targets_obs.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     lib.np_f16_set_timing.argtypes = [C.c_void_p, C.c_int]
     lib.np_f16_set_kernel_variant.argtypes = [C.c_void_p, C.c_int]
+    if hasattr(lib, 'np_f16_set_fleet'):   # (a measurement build loaded through NPF16_LIB may predate the fleet; the built library is checked against EXPORTS)
+        lib.np_f16_set_fleet.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        lib.np_f16_set_fleet_index.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
     lib.np_actor_forward.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_int, C.c_void_p]
     lib.np_planning_inner_loop.argtypes = [C.c_void_p, C.c_int64, C.POINTER(NpF16Io), C.POINTER(NpPlanningLoop), C.c_void_p]

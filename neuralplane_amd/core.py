@@ -92,11 +92,65 @@ def _check_airframe(sd, airframe):
         raise ValueError('checkpoint was written with a different airframe block (np_f16_airframe) than this env was built with')
 
 
-class F16Batch:
-    """N aircraft on one GPU.  `row0` is the global index of local row 0 (sharded batches)."""
+FLEET_MAX_CLASSES = 65536
 
-    def __init__(self, n, config, task, device, seed=0, solver=None, row0=0, blob_path=ASSET_BLOB, aero_1d_tables=None, aero_gemm_order=None):
+
+def fleet_classes(config, airframes=None):
+    """The airframe classes of a fleet as a ctypes array of np_f16_airframe blocks, or None without a fleet: the `airframes` argument, else the
+    scenario key `airframes:` — a list of mappings of np_f16_airframe fields, each like `airframe=` ({} = the F-16).  Needs no device:
+    an empty list, an entry that is no mapping, an unknown field, or `airframes` next to a scenario `airframe` raise ValueError here."""
+    if airframes is None:
+        airframes = getattr(config, 'airframes', None)
+    if airframes is None:
+        return None
+    if getattr(config, 'airframe', None):
+        raise ValueError('airframes (a fleet: one airframe per class) and airframe (one airframe per context) exclude each other')
+    if isinstance(airframes, (str, bytes)) or not hasattr(airframes, '__len__') or hasattr(airframes, 'keys'):
+        raise ValueError('airframes: a list of {np_f16_airframe field: value} mappings, one per class')
+    if not 1 <= len(airframes) <= FLEET_MAX_CLASSES:
+        raise ValueError(f'airframes: a fleet has 1 .. {FLEET_MAX_CLASSES} airframe classes, got {len(airframes)}')
+    arr = (_lib.NpF16Airframe * len(airframes))()
+    for k, c in enumerate(airframes):
+        if c is not None and not hasattr(c, 'keys'):
+            raise ValueError(f'airframes[{k}]: a mapping of np_f16_airframe fields, got {type(c).__name__}')
+        try:
+            arr[k] = _lib.airframe(c)
+        except (ValueError, TypeError) as e:
+            raise ValueError(f'airframes[{k}]: {e}') from None
+    return arr
+
+
+def _check_fleet(sd, classes, index):
+    """A checkpoint continues only on the fleet that wrote it: the same class blocks and the same class for every row (in the manner of
+    _check_airframe; the all-zero block and the spelled-out F-16 are the same class)."""
+    size = C.sizeof(_lib.NpF16Airframe)
+
+    def keys(blob):
+        blob = bytes(blob)
+        f16 = bytes(_lib.airframe({'Heng': 0.0}))
+        return [f16 if not any(blob[o:o + size]) else blob[o:o + size] for o in range(0, len(blob), size)]
+    have, want = sd.get('airframes'), None if classes is None else bytes(classes)
+    if (have is None) != (want is None):
+        raise ValueError('checkpoint was written ' + ('with' if have is not None else 'without') + ' a fleet (airframes), this env was built '
+                         + ('without one' if have is not None else 'with one'))
+    if have is None:
+        return
+    if keys(have) != keys(want):
+        raise ValueError('checkpoint was written with a different fleet (airframes: the np_f16_airframe blocks of the classes differ) than this env was built with')
+    if not torch.equal(sd['airframe_index'].to('cpu', torch.int32), index.to('cpu')):
+        raise ValueError('checkpoint was written with a different fleet (airframe_index: rows fly other classes) than this env has now')
+
+
+class F16Batch:
+    """N aircraft on one GPU.  `row0` is the global index of local row 0 (sharded batches).
+    airframes / airframe_index: a fleet — K airframe classes and the class of every row (see set_fleet)."""
+
+    def __init__(self, n, config, task, device, seed=0, solver=None, row0=0, blob_path=ASSET_BLOB, aero_1d_tables=None, aero_gemm_order=None,
+                 airframes=None, airframe_index=None):
         self.lib = _lib.load()
+        classes = fleet_classes(config, airframes)      # refusals that need no device come first
+        if classes is None and airframe_index is not None:
+            raise ValueError('airframe_index without airframes: the index selects among the classes of a fleet')
         self.device = torch.device(device)
         if self.device.type != 'cuda':
             raise RuntimeError(f"neuralplane_amd runs on MI355X (torch device 'cuda:N'), not on '{device}': "
@@ -148,6 +202,61 @@ class F16Batch:
         # bumped whenever one of the optional output pointers above changes: a HIP graph that baked the old pointers must be
         # re-captured before its next replay (PlanningEnv._step_graph checks it)
         self._io_epoch = 0
+        self.airframes = None          # fleet: the K np_f16_airframe blocks (ctypes array) ...
+        self.airframe_index = None     # ... and int32[n], the class of every row (device tensor the kernels read: kept alive here)
+        if classes is not None:
+            if self.aero_gemm_order:
+                raise ValueError('airframes: a context with aero_gemm_order has no fleet kernels; leave one of the two off')
+            self.set_fleet(classes, airframe_index)
+
+    # -- fleet: per-row airframes ----------------------------------------------------------------
+    def _checked_index(self, airframe_index, k):
+        """airframe_index -> a fresh int32 device tensor of n rows with every value in 0 .. k-1, or ValueError (one host synchronisation)"""
+        idx = torch.as_tensor(airframe_index)
+        if idx.dtype not in (torch.int32, torch.int64, torch.int16, torch.int8, torch.uint8) or idx.dim() != 1 or idx.numel() != self.n:
+            raise ValueError(f'airframe_index: an integer tensor of n = {self.n} rows, got {idx.dtype} {tuple(idx.shape)}')
+        idx = idx.to(self.device)
+        lo, hi = (int(v) for v in torch.stack((idx.min(), idx.max())).tolist())
+        if lo < 0 or hi >= k:
+            raise ValueError(f'airframe_index: values must lie in 0 .. {k - 1} (the fleet has {k} classes), got {lo} .. {hi}')
+        return idx.to(torch.int32).contiguous().clone()     # a private copy: later edits of the caller's tensor cannot slip past the check
+
+    def _store_index(self, idx):
+        """The kernels read the index through a pointer that a launch bakes into its arguments (so does a captured HIP graph): the batch
+        keeps ONE index buffer for its lifetime and writes new values into it in place, on the current stream, behind the launches already
+        enqueued.  Only the first index registers a pointer (and bumps _io_epoch, like every other baked pointer that changes)."""
+        if self.airframe_index is None:
+            _lib.check(self.lib.np_f16_set_fleet_index(self._ctx, idx.data_ptr(), self.n))
+            self.airframe_index = idx
+            self._io_epoch += 1
+        else:
+            self.airframe_index.copy_(idx)
+        self._cache_valid = False
+        self._version += 1
+        self._derived = None
+
+    def set_fleet(self, classes, airframe_index=None):
+        """K airframe classes (ctypes array from fleet_classes) and the class of every row.  airframe_index omitted: (row0 + i) % K, so that
+        a sharded batch flies what the unsharded one flies.  The index is checked before anything changes: a refused one leaves the batch
+        as it was.  Replacing the classes of a batch that already has a fleet moves the device table: _io_epoch is bumped, so that
+        PlanningEnv re-captures its graph; a graph of the caller's own around launch_static must be re-captured by the caller."""
+        if airframe_index is None:
+            airframe_index = ((torch.arange(self.n, dtype=torch.int64, device=self.device) + self.row0) % len(classes)).to(torch.int32)
+        idx = self._checked_index(airframe_index, len(classes))
+        _lib.check(self.lib.np_f16_set_fleet(self._ctx, C.cast(classes, C.c_void_p), len(classes)))
+        self.airframes = classes
+        self._io_epoch += 1
+        self._store_index(idx)
+
+    def set_airframe_index(self, airframe_index):
+        """Replace the class of every row between steps: an integer tensor of n entries in 0 .. K-1.  Checked once, here (one host
+        synchronisation; ValueError on a value outside the table, and the batch keeps its index) — the kernels only clamp.  The values are
+        written into the batch's own index buffer in place, so launches captured in a HIP graph (PlanningEnv.enable_graph, launch_static)
+        fly the new classes from their next replay on.  The cross-step cache is dropped: it holds the atmosphere power of the class that
+        wrote it."""
+        if self.airframes is None:
+            raise ValueError('set_airframe_index: this batch has no fleet (airframes=...)')
+        self._store_index(self._checked_index(airframe_index, len(self.airframes)))
 
     def __del__(self):
         ctx = getattr(self, '_ctx', None)
@@ -432,11 +541,15 @@ class F16Batch:
     def state_dict(self):
         """Everything needed to continue the trajectories bit for bit: state, targets, counters, the flags
         left by the last step and the RNG counter (the RNG is counter-based: no generator state)."""
-        return {'s': self.s.clone(), 'u': self.u.clone(), 'tgt': self.tgt.clone(), 'step_count': self.step_count.clone(),
-                'flags': self.flags.clone(), 'call_idx': int(self.call_idx), 'seed': int(self.seed), 'row0': int(self.row0),
-                'task': self.task, 'n': self.n, 'numerics_spec': NUMERICS_SPEC, 'abi_version': _lib.ABI_VERSION,
-                'aero_gemm_order': self.aero_gemm_order,
-                'airframe': bytes(self.cfg.airframe)}   # np_f16_airframe as built (all zero = the F-16): a resumed run must fly the same aircraft
+        sd = {'s': self.s.clone(), 'u': self.u.clone(), 'tgt': self.tgt.clone(), 'step_count': self.step_count.clone(),
+              'flags': self.flags.clone(), 'call_idx': int(self.call_idx), 'seed': int(self.seed), 'row0': int(self.row0),
+              'task': self.task, 'n': self.n, 'numerics_spec': NUMERICS_SPEC, 'abi_version': _lib.ABI_VERSION,
+              'aero_gemm_order': self.aero_gemm_order,
+              'airframe': bytes(self.cfg.airframe)}   # np_f16_airframe as built (all zero = the F-16): a resumed run must fly the same aircraft
+        if self.airframes is not None:      # a fleet: the K class blocks and the class of every row (absent without a fleet: the keys of old)
+            sd['airframes'] = bytes(self.airframes)
+            sd['airframe_index'] = self.airframe_index.clone()
+        return sd
 
     def load_state_dict(self, sd):
         if sd['n'] != self.n or sd['task'] != self.task:
@@ -444,6 +557,7 @@ class F16Batch:
         _check_numerics_spec(sd)
         _check_gemm_order(sd, self.aero_gemm_order)
         _check_airframe(sd, self.cfg.airframe)
+        _check_fleet(sd, self.airframes, self.airframe_index)
         for k in ('s', 'u', 'tgt', 'step_count'):
             getattr(self, k).copy_(sd[k].to(self.device))
         self.flags = sd['flags'].to(self.device).clone()
@@ -503,7 +617,8 @@ class F16Batch:
 
     def set_kernel_variant(self, variant):
         """'auto' (default: 'latency8' while n <= 16384, 'latency' while n <= 49152, 'latency2' while n <= 98304, then 'pair'),
-        'latency8', 'latency', 'latency2', 'throughput', 'pair' — bit-identical results."""
+        'latency8', 'latency', 'latency2', 'throughput', 'pair' — bit-identical results.  A batch with a fleet runs the throughput-shaped
+        fleet kernel at every n: 'auto' and 'throughput' only."""
         _lib.check(self.lib.np_f16_set_kernel_variant(self._ctx, _lib.KERNEL_VARIANTS[variant]))
 
 

@@ -1,5 +1,5 @@
 // np_env_tu.inc — body of one env-kernel translation unit: #define NP_ENV_TASK / NP_ENV_SOLVER (and NP_ENV_GEMM 1 for the unit of the
-// GEMM-order kernels, numerics option aero_gemm_order), then include this file.
+// GEMM-order kernels, numerics option aero_gemm_order; or NP_ENV_FLEET 1 for the unit of the fleet kernels, f16_fleet_kernel), then include this file.
 // Every variant of f16_env_kernel<NP_ENV_TASK, NP_ENV_SOLVER, ..., NP_ENV_GEMM> the dispatch rule (np_dispatch.h::env_choice) can pick is
 // instantiated here and nowhere else; which one a launch gets is decided by the caller (EnvLaunch::ch), this file only maps flags to template arguments.
 #include "np_f16_env_kernel.h"
@@ -8,6 +8,38 @@
 #define NP_ENV_GEMM 0
 #endif
 
+#ifdef NP_ENV_FLEET
+// the fleet kernels of this task x solver: step (cached or not, inner step / update-only or not) and, in the Euler unit, reset
+namespace npf16 {
+namespace {
+
+template <int S, bool STEP, bool I>
+void launch_fleet(const EnvLaunch &l) {
+    constexpr int T = NP_ENV_TASK;
+    const auto k = l.cached ? f16_fleet_kernel<T, S, STEP, STEP, I> : f16_fleet_kernel<T, S, STEP, false, I>;
+    FleetKArgs fa;
+    static_cast<KArgs &>(fa) = l.a;
+    fa.fleet = l.fleet;
+    const dim3 grid((unsigned)l.ch.grid), block((unsigned)l.ch.block);
+    if (l.timed) hipExtLaunchKernelGGL(k, grid, block, 0, l.st, l.start, l.stop, 0, fa);
+    else hipLaunchKernelGGL(k, grid, block, 0, l.st, fa);
+}
+
+}  // namespace
+
+template <>
+void env_dispatch_fleet<NP_ENV_TASK, NP_ENV_SOLVER>(const EnvLaunch &l) {
+    if (l.step) {
+        if (l.inner) launch_fleet<NP_ENV_SOLVER, true, true>(l);
+        else launch_fleet<NP_ENV_SOLVER, true, false>(l);
+    }
+#if NP_ENV_SOLVER == 0
+    else launch_fleet<0, false, false>(l);
+#endif
+}
+
+}  // namespace npf16
+#else
 namespace npf16 {
 namespace {
 
@@ -60,3 +92,4 @@ void env_dispatch<NP_ENV_TASK, NP_ENV_SOLVER, bool(NP_ENV_GEMM)>(const EnvLaunch
 }
 
 }  // namespace npf16
+#endif

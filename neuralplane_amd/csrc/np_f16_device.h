@@ -42,6 +42,39 @@ struct AirframeVia {
 template <class AP>
 __device__ __forceinline__ AirframeVia<AP> airframe_via(AP &ap) { return AirframeVia<AP>{ap}; }
 
+// Per-row airframes (a fleet, FleetRef in np_f16_types.h): the record of ONE lane's class, table[index[row]], as vector loads — ten
+// global_load_dwordx4 per record, of which the compiler keeps those with a lane somebody reads.  The index is compared unsigned against k and
+// clamped to k - 1 BEFORE it forms an address: whatever the index array holds, nothing outside the table is read (the host rejects such an
+// index long before; this is the second fence).  The r_* reciprocals travel in the record (np_divc takes them as values).
+static_assert(sizeof(Airframe) % 16 == 0, "a fleet record is a whole number of 16-byte vectors");
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ Airframe fleet_airframe(const FleetRef &f, unsigned row) {
+    typedef const int __attribute__((address_space(1))) *gi32;
+    typedef const f32x4 __attribute__((address_space(1))) *gv4;
+    unsigned c = (unsigned)((gi32)(unsigned long long)f.index)[row];
+    c = c < f.k ? c : f.k - 1u;
+    const gv4 rec = (gv4)((unsigned long long)f.table + (unsigned long long)c * sizeof(Airframe));
+    union {
+        Airframe a;
+        f32x4 v[sizeof(Airframe) / 16];
+    } r;
+#pragma unroll
+    for (unsigned j = 0; j < sizeof(Airframe) / 16; j++) r.v[j] = rec[j];
+    return r.a;
+}
+// FleetVia<AP>{ap, row}.get(): the fleet's pointers re-read from the kernel-argument segment behind the MLP phase (as AirframeVia re-reads the
+// constants themselves), then this lane's record; what lives across the asm statements is `ap` and the row number the kernel keeps anyway.
+template <class AP>
+struct FleetVia {
+    AP &ap;
+    unsigned row;
+    __device__ __forceinline__ Airframe get() const {
+        NP_REREAD_ARGS(ap);
+        const FleetRef f = {ap->fleet.table, ap->fleet.index, ap->fleet.k, 0u};
+        return fleet_airframe(f, row);
+    }
+};
+
 // ---------------------------------------------------------------------------------------------
 // MLP evaluation — hifi_F16_AeroData.py:12-37 (MLP.forward, normalize, unnormalize)
 //   Linear: acc = bias; acc = fmaf(W[j][k], x[k], acc), k ascending (numerics spec)
@@ -1088,6 +1121,11 @@ __device__ __forceinline__ void observe(const CFG &cfg, const float (&s)[12], co
     o[20] = 0.0f / 45.0f;  // lef
     o[21] = eas2tas;
 }
+// what observe reads of the scenario constants, for a row of a fleet: the context's airspeed and the airframe record of the row's class
+struct FleetObsCfg {
+    float airspeed;
+    Airframe af;
+};
 
 // Observation noise (numerics spec): 22 normals of (seed, call_idx, global row) from FOUR Philox4x32-10 blocks
 // (counter blocks 2..5) by Box-Muller on 11 pairs.  Every pair takes a 21-bit radius index K1 and a 21-bit direction index K2:

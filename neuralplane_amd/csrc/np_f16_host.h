@@ -252,6 +252,73 @@ inline Airframe make_airframe(const np_f16_airframe &in) {
     return d;
 }
 
+// ---- fleets (np_f16_set_fleet): per-row airframes ---------------------------------------------------------------------------------
+// One record of the device table: make_airframe's constants with the two stretches of padding inside an Airframe (before atm_exp, behind
+// surf_max) zeroed, so that a table is a function of its classes byte for byte.
+// Field by field: a field added to Airframe (np_f16_types.h) must be added below, or every fleet flies it as zero — the size is pinned so
+// that such a change stops here first (160 bytes: 36 floats and the double atm_exp, 4 + 4 bytes of padding).
+static_assert(sizeof(Airframe) == 160, "Airframe changed: copy the new field in fleet_record, then update this size");
+inline Airframe fleet_record(const np_f16_airframe &c) {
+    const Airframe v = make_airframe(c);
+    Airframe r;
+    std::memset(&r, 0, sizeof(r));
+    r.g = v.g; r.mass = v.mass; r.r_mass = v.r_mass; r.B = v.B; r.S = v.S; r.cbar = v.cbar; r.Heng = v.Heng; r.pad_ = v.pad_;
+    r.Jy = v.Jy; r.r_Jy = v.r_Jy; r.Jxz = v.Jxz; r.Jz = v.Jz; r.Jx = v.Jx;
+    r.xc = v.xc; r.cbar_over_B = v.cbar_over_B; r.c1 = v.c1; r.c2 = v.c2; r.c3 = v.c3; r.c4 = v.c4; r.denom = v.denom; r.r_denom = v.r_denom;
+    r.ail_ref = v.ail_ref; r.r_ail_ref = v.r_ail_ref; r.rud_ref = v.rud_ref; r.r_rud_ref = v.r_rud_ref;
+    r.atm_lapse = v.atm_lapse; r.rho0 = v.rho0; r.atm_exp = v.atm_exp;
+    r.lag_keep = v.lag_keep; r.lag_new = v.lag_new; r.thrust_frac = v.thrust_frac; r.thrust_max = v.thrust_max;
+    r.thrust_unit = v.thrust_unit; r.r_thrust_unit = v.r_thrust_unit;
+    for (int k = 0; k < 3; k++) r.surf_max[k] = v.surf_max[k];
+    return r;
+}
+
+// The table of a fleet: record k = fleet_record(classes[k]) (an all-zero block = the F-16).  false: `err` says why — the class count, or the
+// first class airframe_error refuses, by number.
+inline bool fleet_table(const np_f16_airframe *classes, int64_t k, std::vector<Airframe> &out, std::string &err) {
+    out.clear();
+    if (k < 1 || k > FLEET_MAX_CLASSES) {
+        err = "fleet: the number of airframe classes must be 1 .. " + std::to_string(FLEET_MAX_CLASSES) + " (got " + std::to_string(k) + ")";
+        return false;
+    }
+    if (!classes) {
+        err = "fleet: null class table";
+        return false;
+    }
+    for (int64_t c = 0; c < k; c++) {
+        if (airframe_is_zero(classes[c])) continue;
+        if (const char *e = airframe_error(classes[c])) {
+            err = "fleet: class " + std::to_string(c) + ": " + e;
+            return false;
+        }
+    }
+    out.resize((size_t)k);
+    for (int64_t c = 0; c < k; c++) out[(size_t)c] = fleet_record(classes[c]);
+    return true;
+}
+
+// What a context with a fleet cannot be or do: null, or the refusal (every message names the fleet).  combat / gemm_order / variant: the
+// context's; the fleet kernels are the single-set throughput shape of the MLP and the table numerics.
+inline const char *fleet_context_error(bool combat, bool gemm_order, int variant) {
+    if (combat) return "fleet: SingleCombat contexts have no fleet kernels (one airframe per context: np_f16_combat_cfg.airframe)";
+    if (gemm_order) return "fleet: a context with aero_gemm_order has no fleet kernels (the fleet kernels are built for the default order of the aero nets)";
+    if (variant != NP_KERNEL_AUTO && variant != NP_KERNEL_THROUGHPUT)
+        return "fleet: a context with a fleet runs the throughput-shaped fleet kernel at every n (np_f16_set_kernel_variant: NP_KERNEL_AUTO or NP_KERNEL_THROUGHPUT only)";
+    return nullptr;
+}
+// np_planning_inner_loop on a context with a fleet: launch by launch only
+inline const char *fleet_planning_error(int mode) {
+    if (mode >= NP_PLANNING_PERSISTENT)
+        return "np_planning_loop: a context with a fleet runs launch by launch (the persistent kernel and its guest / queue / dual schedules read one airframe per context); mode must be NP_PLANNING_AUTO or NP_PLANNING_LAUNCHES";
+    return nullptr;
+}
+// a launch of `n` rows starting at row `off` of the index np_f16_set_fleet_index registered for `index_n` rows
+inline const char *fleet_launch_error(bool have_index, int64_t index_n, int64_t off, int64_t n) {
+    if (!have_index) return "fleet: no airframe index (np_f16_set_fleet_index) for a context with a fleet";
+    if (off < 0 || off + n > index_n) return "fleet: the launch covers more rows than the airframe index registered with np_f16_set_fleet_index";
+    return nullptr;
+}
+
 inline DevCfg make_devcfg(const np_f16_cfg &c) {
     DevCfg d;
     d.af = make_airframe(c.airframe);

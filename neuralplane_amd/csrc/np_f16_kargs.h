@@ -71,4 +71,17 @@ struct KArgs {
     unsigned long long *trace;
 };
 
+// The argument record of the fleet kernels (f16_fleet_kernel, np_f16_env_kernel.h): the same record — at offset 0 of the segment, so everything
+// that reads `ap->...` reads what it reads in the one-airframe kernels — with the fleet behind it.  The one-airframe kernels keep KArgs as it is.
+struct FleetKArgs : KArgs {
+    FleetRef fleet;
+};
+typedef const FleetKArgs __attribute__((address_space(4))) *FleetKArgsC;
+
+// the airframe record of lane `row` where the code stands (f16_fleet_kernel: atmos_pow, control_lag, the observation of a reset)
+__device__ __forceinline__ Airframe fleet_airframe_of(FleetKArgsC ap, unsigned row) {
+    const FleetRef f = {ap->fleet.table, ap->fleet.index, ap->fleet.k, 0u};
+    return fleet_airframe(f, row);
+}
+
 }  // namespace npf16

@@ -105,6 +105,15 @@ __global__ __launch_bounds__(BLOCK) void f16_derived_kernel(const float *__restr
     f16_derived_rows<GEMM>(sp, up, ld, out, ld_out, n, airspeed, tables, wt, af);
 }
 
+// a context with a fleet (np_f16_set_fleet): every row with the airframe record of its class.  Off the hot path: the record is loaded up front.
+__global__ __launch_bounds__(BLOCK) void f16_derived_fleet_kernel(const float *__restrict__ sp, const float *__restrict__ up,
+                                                                  long long ld, float *__restrict__ out, long long ld_out,
+                                                                  long long n, float airspeed, int tables, AeroWeights wt, FleetRef fleet) {
+    const long long i = (long long)blockIdx.x * BLOCK + threadIdx.x;
+    const Airframe af = fleet_airframe(fleet, (unsigned)(i < n ? i : n - 1));
+    f16_derived_rows<false>(sp, up, ld, out, ld_out, n, airspeed, tables, wt, af);
+}
+
 // hifi_F16.hifi_C / hifi_damping / hifi_C_lef / hifi_damping_lef / hifi_rudder / hifi_ailerons / hifi_other_coeffs
 // (envs/models/F16/hifi_F16_AeroData.py:745-822) for arbitrary (alpha, beta, el) in degrees: the same normalisation and net
 // bodies nlplant runs (so what this returns IS what the step kernels use), out[43][ld_out] in the reference's evaluation order
@@ -143,10 +152,11 @@ __global__ __launch_bounds__(BLOCK) void f16_aero_kernel(const float *__restrict
 // ACTION = false: targets from tp[3][ld].  ACTION = true (PlanningEnv.step's prelude, planning_env.py:146-152): targets = (pitch, heading,
 // vt) + clamp(action, -1, 1) * (0.3, 0.3, 30) — one product and one sum per element as the reference's torch expressions — written to
 // tgt_out[3][ld] as well
-template <bool ACTION>
-__global__ __launch_bounds__(BLOCK) void f16_lowlevel_obs_kernel(const float *__restrict__ sp, const float *__restrict__ up,
-                                                                 const float *__restrict__ tp, long long ld, float *__restrict__ obs,
-                                                                 long long n, DevCfg cfg, long long act_stride, float *__restrict__ tgt_out) {
+// FLEET: the EAS2TAS of a row takes the atmosphere constants of the row's class (a context with a fleet) instead of cfg.af
+template <bool ACTION, bool FLEET>
+__device__ __forceinline__ void f16_lowlevel_obs_rows(const float *__restrict__ sp, const float *__restrict__ up,
+                                                      const float *__restrict__ tp, long long ld, float *__restrict__ obs,
+                                                      long long n, const DevCfg &cfg, long long act_stride, float *__restrict__ tgt_out, const FleetRef &fleet) {
     __shared__ float tile[BLOCK * OBS_LD];
     const int t = threadIdx.x;
     const long long i0 = (long long)blockIdx.x * BLOCK, i = i0 + t;
@@ -173,7 +183,8 @@ __global__ __launch_bounds__(BLOCK) void f16_lowlevel_obs_kernel(const float *__
     float tt;
     trig_of(s, tr, tt);
     float o[22];
-    observe<1>(cfg, s, u, tgt, tr, o);
+    if constexpr (FLEET) observe<1>(FleetObsCfg{cfg.airspeed, fleet_airframe(fleet, (unsigned)ic)}, s, u, tgt, tr, o);
+    else observe<1>(cfg, s, u, tgt, tr, o);
 #pragma unroll
     for (int k = 0; k < 22; k++) tile[t * OBS_LD + k] = o[k];
     __syncthreads();
@@ -188,6 +199,18 @@ __global__ __launch_bounds__(BLOCK) void f16_lowlevel_obs_kernel(const float *__
             dst[L] = tile[r * OBS_LD + c];
         }
     }
+}
+template <bool ACTION>
+__global__ __launch_bounds__(BLOCK) void f16_lowlevel_obs_kernel(const float *__restrict__ sp, const float *__restrict__ up,
+                                                                 const float *__restrict__ tp, long long ld, float *__restrict__ obs,
+                                                                 long long n, DevCfg cfg, long long act_stride, float *__restrict__ tgt_out) {
+    f16_lowlevel_obs_rows<ACTION, false>(sp, up, tp, ld, obs, n, cfg, act_stride, tgt_out, FleetRef{});
+}
+template <bool ACTION>
+__global__ __launch_bounds__(BLOCK) void f16_lowlevel_obs_fleet_kernel(const float *__restrict__ sp, const float *__restrict__ up,
+                                                                       const float *__restrict__ tp, long long ld, float *__restrict__ obs,
+                                                                       long long n, DevCfg cfg, long long act_stride, float *__restrict__ tgt_out, FleetRef fleet) {
+    f16_lowlevel_obs_rows<ACTION, true>(sp, up, tp, ld, obs, n, cfg, act_stride, tgt_out, fleet);
 }
 
 // cached coefficients of a reset aircraft (alpha = beta = 0) -> out[14]; run once per context
@@ -318,6 +341,12 @@ struct np_f16_ctx {
     bool plan_unchecked = false;
     const char *plan_unchecked_mode = "";
     int num_cus = 0;  // multiProcessorCount of the context's device
+    // fleet (np_f16_set_fleet / np_f16_set_fleet_index): the class table is owned by the context, the index by the caller
+    Airframe *d_fleet = nullptr;
+    int32_t fleet_k = 0;
+    const int32_t *fleet_index = nullptr;
+    int64_t fleet_n = 0;
+    FleetRef fleet_ref(int64_t off) const { return FleetRef{d_fleet, fleet_index ? fleet_index + off : nullptr, (unsigned)fleet_k, 0u}; }
 };
 
 namespace {
@@ -453,8 +482,9 @@ int pair_waves_override() {
         else hipLaunchKernelGGL((__VA_ARGS__), grid, block, lds_pad, st, ARGS);                                       \
     } while (0)
 
+// fleet_off: contexts with a fleet, launches on a slice of the batch (np_planning_inner_loop's row groups): the slice's first row in the index
 template <bool STEP>
-int launch_env(np_f16_ctx *ctx, int64_t n, const np_f16_io *io, void *stream) {
+int launch_env(np_f16_ctx *ctx, int64_t n, const np_f16_io *io, void *stream, int64_t fleet_off = 0) {
     if (!ctx || !io) return fail("null ctx/io");
     if (ctx->combat) return fail("combat context: use np_f16_combat_reset / np_f16_combat_step");
     if (n <= 0) return 0;
@@ -471,6 +501,11 @@ int launch_env(np_f16_ctx *ctx, int64_t n, const np_f16_io *io, void *stream) {
     if (update_only && (!io->action || io->act_stride < 4)) return fail("update needs action (>=4 columns)");
     if (io->done_out == io->done_in || io->bad_out == io->bad_in || io->timeout_out == io->timeout_in)
         return fail("flag outputs may not alias flag inputs");
+    const bool fleet = ctx->fleet_k > 0;
+    if (fleet) {
+        if (const char *e = fleet_context_error(ctx->combat, ctx->gemm_order, ctx->variant)) return fail(e);
+        if (const char *e = fleet_launch_error(ctx->fleet_index != nullptr, ctx->fleet_n, fleet_off, n)) return fail(e);
+    }
     DeviceGuard guard;
     NP_HIP(guard.enter(ctx->device));
     KArgs a;
@@ -501,8 +536,10 @@ int launch_env(np_f16_ctx *ctx, int64_t n, const np_f16_io *io, void *stream) {
     // batches of the MLP numerics (the table mode's classes are too short to split further).  latency2: two waves per tile, above the
     // four-wave variant's single generation (both numerics; Euler).  latency4w: four waves per tile at four waves per SIMD, one generation
     // of four tiles per CU (MLP numerics; the table mode's kernels are not built for it).
-    const npdispatch::EnvChoice ch = npdispatch::env_choice(n, ctx->num_cus, STEP, ctx->solver, ctx->cfg.aero_1d_tables != 0, ctx->variant,
-                                                            env_kernel_override(), pair_waves_override(), BLOCK, ctx->gemm_order);
+    // (a context with a fleet: the throughput shape at every n, whatever the process-wide overrides say)
+    const npdispatch::EnvChoice ch = fleet ? npdispatch::env_choice(n, ctx->num_cus, STEP, ctx->solver, ctx->cfg.aero_1d_tables != 0, NP_KERNEL_THROUGHPUT, NP_KERNEL_AUTO, 0, BLOCK)
+                                           : npdispatch::env_choice(n, ctx->num_cus, STEP, ctx->solver, ctx->cfg.aero_1d_tables != 0, ctx->variant,
+                                                                    env_kernel_override(), pair_waves_override(), BLOCK, ctx->gemm_order);
     a.cus = ctx->num_cus;
     hipStream_t st = (hipStream_t)stream;
     // Pair variant at three waves per SIMD (six workgroups per CU) or at two (four per CU)?  Measured per grid size (heading,
@@ -524,13 +561,16 @@ int launch_env(np_f16_ctx *ctx, int64_t n, const np_f16_io *io, void *stream) {
     EnvLaunch l;
     l.a = a; l.ch = ch; l.st = st; l.timed = timed; l.start = ev.first; l.stop = ev.second;
     l.step = STEP; l.inner = STEP && a.inner; l.cached = cached;
+    l.fleet = fleet ? ctx->fleet_ref(fleet_off) : FleetRef{};
     using Fn = void (*)(const EnvLaunch &);
     static constexpr Fn table[2][3][2] = {   // [gemm][task][solver]
         {{env_dispatch<0, 0, false>, env_dispatch<0, 1, false>}, {env_dispatch<1, 0, false>, env_dispatch<1, 1, false>}, {env_dispatch<2, 0, false>, env_dispatch<2, 1, false>}},
         {{env_dispatch<0, 0, true>, env_dispatch<0, 1, true>}, {env_dispatch<1, 0, true>, env_dispatch<1, 1, true>}, {env_dispatch<2, 0, true>, env_dispatch<2, 1, true>}}};
     const int solver = STEP ? ctx->solver : 0;
     if (ctx->task < 0 || ctx->task > 2 || solver < 0 || solver > 1) return fail("bad task/solver");
-    table[ctx->gemm_order ? 1 : 0][ctx->task][solver](l);
+    static constexpr Fn fleet_table_[3][2] = {{env_dispatch_fleet<0, 0>, env_dispatch_fleet<0, 1>}, {env_dispatch_fleet<1, 0>, env_dispatch_fleet<1, 1>}, {env_dispatch_fleet<2, 0>, env_dispatch_fleet<2, 1>}};
+    if (fleet) fleet_table_[ctx->task][solver](l);
+    else table[ctx->gemm_order ? 1 : 0][ctx->task][solver](l);
     NP_HIP(hipGetLastError());
     lease.commit();
     return 0;
@@ -748,6 +788,7 @@ void np_f16_ctx_destroy(np_f16_ctx *ctx) {
         if (guard.enter(ctx->device) == hipSuccess) {
             if (ctx->d_reset_coef) (void)hipFree(ctx->d_reset_coef);  // hipFree waits for kernels still reading the buffers
             if (ctx->d_weights) (void)hipFree(ctx->d_weights);
+            if (ctx->d_fleet) (void)hipFree(ctx->d_fleet);
         }
     }
     for (auto &e : ctx->events) {
@@ -788,6 +829,11 @@ int np_f16_derived(np_f16_ctx *ctx, int64_t n, const float *s, const float *u, i
     DeviceGuard guard;
     NP_HIP(guard.enter(ctx->device));
     const dim3 grid((unsigned)((n + BLOCK - 1) / BLOCK)), block(BLOCK);
+    if (ctx->fleet_k > 0) {
+        if (const char *e = fleet_launch_error(ctx->fleet_index != nullptr, ctx->fleet_n, 0, n)) return fail(e);
+        hipLaunchKernelGGL(f16_derived_fleet_kernel, grid, block, 0, (hipStream_t)stream, s, u, (long long)ld, out, (long long)ld_out, (long long)n,
+                           ctx->cfg.airspeed, ctx->cfg.aero_1d_tables, ctx->wt, ctx->fleet_ref(0));
+    } else
     hipLaunchKernelGGL((ctx->gemm_order ? f16_derived_kernel<true> : f16_derived_kernel<false>), grid, block, 0, (hipStream_t)stream, s, u,
                        (long long)ld, out, (long long)ld_out, (long long)n, ctx->cfg.airspeed, ctx->cfg.aero_1d_tables, ctx->wt, ctx->combat ? ctx->ccfg.af : ctx->cfg.af);
     NP_HIP(hipGetLastError());
@@ -816,6 +862,11 @@ int np_f16_lowlevel_obs(np_f16_ctx *ctx, int64_t n, const float *s, const float 
     DeviceGuard guard;
     NP_HIP(guard.enter(ctx->device));
     const dim3 grid((unsigned)((n + BLOCK - 1) / BLOCK)), block(BLOCK);
+    if (ctx->fleet_k > 0) {
+        if (const char *e = fleet_launch_error(ctx->fleet_index != nullptr, ctx->fleet_n, 0, n)) return fail(e);
+        hipLaunchKernelGGL(f16_lowlevel_obs_fleet_kernel<false>, grid, block, 0, (hipStream_t)stream, s, u, tgt3, (long long)ld, obs, (long long)n,
+                           ctx->cfg, 0ll, (float *)nullptr, ctx->fleet_ref(0));
+    } else
     hipLaunchKernelGGL(f16_lowlevel_obs_kernel<false>, grid, block, 0, (hipStream_t)stream, s, u, tgt3, (long long)ld, obs, (long long)n,
                        ctx->cfg, 0ll, (float *)nullptr);
     NP_HIP(hipGetLastError());
@@ -831,6 +882,11 @@ int np_planning_targets_obs(np_f16_ctx *ctx, int64_t n, const float *s, const fl
     DeviceGuard guard;
     NP_HIP(guard.enter(ctx->device));
     const dim3 grid((unsigned)((n + BLOCK - 1) / BLOCK)), block(BLOCK);
+    if (ctx->fleet_k > 0) {
+        if (const char *e = fleet_launch_error(ctx->fleet_index != nullptr, ctx->fleet_n, 0, n)) return fail(e);
+        hipLaunchKernelGGL(f16_lowlevel_obs_fleet_kernel<true>, grid, block, 0, (hipStream_t)stream, s, u, action, (long long)ld, obs, (long long)n,
+                           ctx->cfg, (long long)act_stride, tgt3, ctx->fleet_ref(0));
+    } else
     hipLaunchKernelGGL(f16_lowlevel_obs_kernel<true>, grid, block, 0, (hipStream_t)stream, s, u, action, (long long)ld, obs, (long long)n,
                        ctx->cfg, (long long)act_stride, tgt3);
     NP_HIP(hipGetLastError());
@@ -1200,7 +1256,9 @@ int np_planning_inner_loop(np_f16_ctx *ctx, int64_t n, const np_f16_io *io, cons
                    : std::strcmp(e, "queue") == 0 ? NP_PLANNING_PERSISTENT_QUEUE : std::strcmp(e, "guests") == 0 ? NP_PLANNING_PERSISTENT_GUESTS : std::strcmp(e, "dual") == 0 ? NP_PLANNING_PERSISTENT_DUAL : mode;
         }
         if (const char *e = std::getenv("NP_PLANNING_WAVES")) waves = atoi(e) == 8 ? 8 : atoi(e) == 4 ? 4 : waves;
-        const bool eligible = ctx->solver == 0 && !ctx->cfg.aero_1d_tables && !ctx->gemm_order && io->coef_cache && !io->rand_u && !io->noise && io->reward && planning_persistent_built(ctx->task);
+        if (ctx->fleet_k > 0)
+            if (const char *e = fleet_planning_error(mode)) return fail(e);
+        const bool eligible = ctx->solver == 0 && !ctx->cfg.aero_1d_tables && !ctx->gemm_order && ctx->fleet_k == 0 && io->coef_cache && !io->rand_u && !io->noise && io->reward && planning_persistent_built(ctx->task);
         if (mode >= NP_PLANNING_PERSISTENT && !eligible)
             return fail("np_planning_loop: the persistent kernel serves tracking contexts (the reference's PlanningEnv task) with the Euler solver and the MLP numerics, and needs coef_cache / reward buffers");
         if (mode == NP_PLANNING_AUTO) {
@@ -1279,7 +1337,7 @@ int np_planning_inner_loop(np_f16_ctx *ctx, int64_t n, const np_f16_io *io, cons
             q.reward_task = io->reward_task ? io->reward_task + r0 : nullptr;
             q.ll_tgt = last ? nullptr : lp->ll_tgt + r0;
             q.ll_obs = last ? nullptr : lp->ll_obs[b] + r0 * npact::OBS;
-            if (launch_env<true>(ctx, m, &q, (void *)sg)) rc = 1;
+            if (launch_env<true>(ctx, m, &q, (void *)sg, r0)) rc = 1;
         }
     }
     for (int g = 1; g < groups; g++) {
@@ -1453,7 +1511,49 @@ int np_f16_set_kernel_variant(np_f16_ctx *ctx, int variant) {
         return fail("unknown kernel variant");
     if (ctx->gemm_order && variant == NP_KERNEL_PAIR)
         return fail("NP_KERNEL_PAIR: a context with aero_gemm_order has single-set kernels only (throughput and latency variants)");
+    if (ctx->fleet_k > 0)
+        if (const char *e = fleet_context_error(ctx->combat, ctx->gemm_order, variant)) return fail(e);
     ctx->variant = variant;
+    return 0;
+}
+
+int np_f16_set_fleet(np_f16_ctx *ctx, const np_f16_airframe *classes, int32_t k) {
+    if (!ctx) return fail("null ctx");
+    if (const char *e = fleet_context_error(ctx->combat, ctx->gemm_order, ctx->variant)) return fail(e);
+    std::vector<Airframe> table;
+    if (k != 0) {
+        std::string err;
+        if (!fleet_table(classes, k, table, err)) return fail(err);
+    }
+    DeviceGuard guard;
+    NP_HIP(guard.enter(ctx->device));
+    Airframe *d_new = nullptr;
+    if (k != 0) {
+        NP_HIP(hipMalloc(&d_new, sizeof(Airframe) * table.size()));
+        const hipError_t e = hipMemcpy(d_new, table.data(), sizeof(Airframe) * table.size(), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(d_new);
+            NP_HIP(e);
+        }
+    }
+    NP_HIP(hipDeviceSynchronize());   // launches that still read the previous table
+    if (ctx->d_fleet) (void)hipFree(ctx->d_fleet);
+    ctx->d_fleet = d_new;
+    ctx->fleet_k = k;
+    if (k == 0) {
+        ctx->fleet_index = nullptr;
+        ctx->fleet_n = 0;
+    }
+    return 0;
+}
+
+int np_f16_set_fleet_index(np_f16_ctx *ctx, const int32_t *device_index, int64_t n) {
+    if (!ctx) return fail("null ctx");
+    if (ctx->fleet_k <= 0) return fail("np_f16_set_fleet_index: the context has no fleet (np_f16_set_fleet comes first)");
+    if (n < 0 || (n > 0 && !device_index)) return fail("np_f16_set_fleet_index: fleet index of n rows needs a device pointer, n >= 0");
+    if (((uintptr_t)device_index) & 3) return fail("np_f16_set_fleet_index: the fleet index must be 4-byte aligned (int32)");
+    ctx->fleet_index = n > 0 ? device_index : nullptr;
+    ctx->fleet_n = n;
     return 0;
 }
 

@@ -25,6 +25,8 @@ struct AeroWeights {
 // (envs/models/F16/F16_dynamics.py:22-35,61-76,114-116; envs/models/F16_model.py:52-62), rounded to fp32 on the host exactly where the
 // literal expressions round (derived constants folded in double first: np_f16_host.h::make_airframe).  r_* = RN(1 / x) of a divisor
 // (np_divc).  The defaults are the F-16 literals: a context built without an airframe block computes what the literals computed, bit for bit.
+// A new field goes into three places: here, make_airframe and fleet_record (np_f16_host.h: the record of a fleet's table is copied field by
+// field so that its padding is zero; a static_assert on the size stands there).
 struct Airframe {
     float g, mass, r_mass, B, S, cbar, Heng, pad_;
     float Jy, r_Jy, Jxz, Jz, Jx;
@@ -35,6 +37,15 @@ struct Airframe {
     float lag_keep, lag_new, thrust_frac, thrust_max, thrust_unit, r_thrust_unit, surf_max[3];   // u' = 0.9 u + 0.1 a * scale
     NP_DEVICE_INLINE const Airframe &get() const { return *this; }
 };
+
+// A fleet (np_f16_set_fleet / np_f16_set_fleet_index): K airframe records in device memory, each exactly what make_airframe gives for its
+// class (np_f16_host.h::fleet_table; padding bytes zero), and the class of every row of the batch.  Row i flies table[index[i]].
+struct FleetRef {
+    const Airframe *table;   // [k], 16-byte aligned (records are whole 16-byte vectors: the kernels load them as such)
+    const int *index;        // [rows of the launch]
+    unsigned k, pad_;
+};
+constexpr int FLEET_MAX_CLASSES = 65536;
 
 // Scenario constants, pre-rounded on the host exactly where the reference rounds them.
 struct DevCfg {

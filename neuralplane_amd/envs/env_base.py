@@ -7,22 +7,29 @@ reference syncs >= 8 times per step through torch.any()/print and torch.sum() si
 """
 import torch
 
-from ..core import F16Batch
+from ..core import F16Batch, fleet_classes
 from .spaces import Env
 from .utils.utils import parse_config
 
 
 class BaseEnv(Env):
     def __init__(self, num_envs=10, config='heading', model='F16', random_seed=None, device='cuda:0', row0=0,
-                 aero_1d_tables=None, solver=None, weights=None, airframe=None, aero_gemm_order=None):
+                 aero_1d_tables=None, solver=None, weights=None, airframe=None, aero_gemm_order=None, airframes=None, airframe_index=None):
         """airframe (not a reference argument): {np_f16_airframe field: value} for every constant that differs from the F-16's — mass, Jx,
         Jy, Jz, Jxz, S, B, cbar, xcg, xcgr, Heng, g, ail_ref, rud_ref, the atmosphere and command scales (include/neuralplane_amd.h) —,
         or the scenario YAML's `airframe:` mapping; together with `weights` (another NPF16MLP blob of the same topology) that is another
-        aircraft on the same kernels.  Parity of a non-F-16 airframe is unpinned: the reference has none."""
+        aircraft on the same kernels.  Parity of a non-F-16 airframe is unpinned: the reference has none.
+        airframes / airframe_index (a fleet, instead of airframe): a list of such mappings, one per airframe class ({} = the F-16; or the
+        scenario YAML's `airframes:` list), and an int32 tensor of n rows naming the class each row flies — omitted: (row0 + i) % K.  Every row
+        then computes what it computes in an env built with airframe=<its class>; set_airframe_index() replaces the index between steps."""
         super().__init__()
         self.config = parse_config(config)
+        if airframe is not None and airframes is not None:
+            raise ValueError('airframes (a fleet: one airframe per class) and airframe (one airframe per context) exclude each other')
         if airframe is not None:
             self.config.airframe = dict(airframe)
+        fleet_classes(self.config, airframes)      # a fleet that cannot be built is refused here, before any device is touched
+        self._airframes, self._airframe_index = airframes, airframe_index
         self.num_envs = num_envs
         self.num_agents = getattr(self.config, 'num_agents', 100)
         self.n = self.num_agents * self.num_envs
@@ -45,7 +52,9 @@ class BaseEnv(Env):
         self._batch = F16Batch(self.n, self.config, task, self.device, seed=seed, row0=self._row0,
                                aero_1d_tables=self._aero_1d_tables, solver=self._solver,
                                **({'blob_path': self._weights} if self._weights else {}),
-                               **({'aero_gemm_order': self._aero_gemm_order} if self._aero_gemm_order is not None else {}))
+                               **({'aero_gemm_order': self._aero_gemm_order} if self._aero_gemm_order is not None else {}),
+                               **({'airframes': self._airframes} if self._airframes is not None else {}),
+                               **({'airframe_index': self._airframe_index} if self._airframe_index is not None else {}))
         self.device = self._batch.device
         return self._batch
 
@@ -131,6 +140,10 @@ class BaseEnv(Env):
         f = self._batch.flags
         event = -200.0 * f[1].to(torch.float32) + 200.0 * f[0].to(torch.float32)
         return r, event
+
+    def set_airframe_index(self, airframe_index):
+        """A fleet: replace the class every row flies (int tensor of n rows in 0 .. K-1; ValueError on a value outside) between steps."""
+        self._batch.set_airframe_index(airframe_index)
 
     def state_dict(self):
         """Env-state checkpoint (tensors on the env device); see F16Batch.state_dict."""

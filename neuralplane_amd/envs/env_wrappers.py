@@ -47,9 +47,11 @@ class VecEnv(ABC):
 
 
 class GPUVecEnv(VecEnv):
-    def __init__(self, env_fns):
+    def __init__(self, env_fns, airframes=None, airframe_index=None):
+        """airframes / airframe_index (a fleet, BaseEnv): handed through to the env factory as keyword arguments when given."""
         assert len(env_fns) == 1, 'GPUVecEnv wraps exactly one batched env'
-        self.env = self.gpu_vec_env = env_fns[0]()      # `gpu_vec_env`: the attribute name of the reference (env_wrappers.py:88)
+        fleet = {k: v for k, v in (('airframes', airframes), ('airframe_index', airframe_index)) if v is not None}
+        self.env = self.gpu_vec_env = env_fns[0](**fleet)      # `gpu_vec_env`: the attribute name of the reference (env_wrappers.py:88)
         self.num_envs = self.env.num_envs
         self.agents = self.num_agents = self.env.num_agents
         self.n = self.env.n
@@ -61,6 +63,9 @@ class GPUVecEnv(VecEnv):
 
     def _shape(self, x, k):
         return x.reshape(self.num_envs, self.num_agents, k)
+
+    def set_airframe_index(self, airframe_index):
+        self.env.set_airframe_index(airframe_index)
 
     def reset(self):
         obs = self.env.reset()
@@ -107,8 +112,8 @@ class PinnedVecEnv(GPUVecEnv):
     The returned arrays are VIEWS of the ring: they stay valid until `ring` further `step`/`reset` calls (default 2 — the
     reference's runners copy what they keep: `buffer.obs[step + 1] = obs.copy()`, runner/F16sim_runner.py:123-154)."""
 
-    def __init__(self, env_fns, ring=2):
-        super().__init__(env_fns)
+    def __init__(self, env_fns, ring=2, **fleet):
+        super().__init__(env_fns, **fleet)
         self._ring = [dict() for _ in range(max(1, int(ring)))]
         self._slot = 0
         self._act_host = None

@@ -19,9 +19,13 @@ from .utils.utils import parse_config
 
 
 class SingleCombatEnv(Env):
-    def __init__(self, num_envs=1, config='selfplay', random_seed=None, device='cuda:0', env0=0, aero_1d_tables=None, airframe=None, aero_gemm_order=None):
+    def __init__(self, num_envs=1, config='selfplay', random_seed=None, device='cuda:0', env0=0, aero_1d_tables=None, airframe=None, aero_gemm_order=None,
+                 airframes=None, airframe_index=None):
         super().__init__()
         self.config = parse_config(config)
+        if airframes is not None or airframe_index is not None or getattr(self.config, 'airframes', None) is not None:
+            raise ValueError('airframes / airframe_index: SingleCombatEnv has no fleet kernels (one airframe per context: airframe=...); '
+                             'a fleet of per-row airframes is for ControlEnv and PlanningEnv')
         if aero_gemm_order or getattr(self.config, 'aero_gemm_order', 0):
             raise ValueError('aero_gemm_order: SingleCombatEnv has no GEMM-order kernels (its kernels run the two-set bodies); leave the option off')
         if airframe is not None:        # {np_f16_airframe field: value}: see BaseEnv
