@@ -511,6 +511,43 @@ int np_dispatch_plan_gemm(int64_t n, int32_t num_cus, int32_t step, int32_t solv
  * on the host — no device needed.  Returns the number of floats (out may be NULL to ask for it), -1 on a bad blob or a short buffer. */
 int64_t np_f16_pack_kblob_gemm(const void *weights_blob, size_t nbytes, float *out, int64_t cap);
 
+/* Open-loop model rollout (a new symbol and record within ABI 16; no earlier record changes): `horizon` applications of F16Model.update
+ * (envs/models/F16_model.py:51-67: clamp, control lag, one integrator step) to a caller-supplied action sequence, as ONE launch — what a
+ * look-ahead (MPC, MPPI, a shooting planner) writes as `for t in range(H): model.update(a[t])` on a copy of the state.  A pure function of
+ * (s0, u0, actions): no random numbers, no observation, reward, termination or auto-reset, and nothing of the context is written (state,
+ * flags, step counters, targets, call index and the cross-step coefficient cache are the caller's np_f16_io buffers, which this call never
+ * sees).  Bit-identical to `horizon` np_f16_step launches with inner_step = NP_INNER_UPDATE_ONLY.
+ *   rows: n0 start rows fan out into n0 * fanout output rows; output row r starts from start row r / fanout and follows ITS OWN actions.
+ *   actions: step t, row r reads the four floats at actions + t * act_step_stride + r * act_row_stride (strides in floats);
+ *            act_step_stride = 0 holds the step-0 action for all `horizon` steps.
+ *   s_traj (optional, needs record_every >= 1): record j = the state after step (j + 1) * record_every, as [12][ld_out] at
+ *            s_traj + j * traj_step_stride, for j < horizon / record_every.
+ *   shape: NP_ROLLOUT_AUTO picks by n0 * fanout and the device's CU count (np_f16_rollout_shape); both shapes compute the same bits.
+ * Everything is checked on the host before the launch (np_last_error names the field).  Refused by name: a context with a fleet, with
+ * aero_gemm_order, with aero_1d_tables, a SingleCombat context, and NP_ROLLOUT_SPLIT on an rk4 context.  cfg.airframe is honoured. */
+#define NP_ROLLOUT_AUTO 0
+#define NP_ROLLOUT_THROUGHPUT 1 /* 128-row workgroups of two waves sharing one weight stream (two-set bodies); Euler and rk4 */
+#define NP_ROLLOUT_SPLIT 2      /* eight waves per 64-row tile, for grids that would leave most CUs idle; Euler only */
+typedef struct np_f16_rollout_io {
+    const float *s0, *u0; int64_t ld0;          /* start state [12][ld0], controls [5][ld0]; n0 rows */
+    const float *actions; int64_t act_step_stride, act_row_stride;   /* floats; step stride 0 = held */
+    int32_t horizon, fanout, record_every, shape;                     /* shape: 0 auto, 1 throughput, 2 split */
+    float *s_out, *u_out; int64_t ld_out;       /* end state of the n0*fanout rows */
+    float *s_traj; int64_t traj_step_stride;    /* optional: state after steps record_every, 2*record_every, ... */
+} np_f16_rollout_io;
+#ifdef __cplusplus
+#define NP_STATIC_ASSERT static_assert
+#else
+#define NP_STATIC_ASSERT _Static_assert
+#endif
+NP_STATIC_ASSERT(sizeof(np_f16_rollout_io) == 104, "np_f16_rollout_io is 104 bytes");
+NP_STATIC_ASSERT(offsetof(np_f16_rollout_io, actions) == 24 && offsetof(np_f16_rollout_io, horizon) == 48 && offsetof(np_f16_rollout_io, shape) == 60, "np_f16_rollout_io layout");
+NP_STATIC_ASSERT(offsetof(np_f16_rollout_io, s_out) == 64 && offsetof(np_f16_rollout_io, ld_out) == 80 && offsetof(np_f16_rollout_io, traj_step_stride) == 96, "np_f16_rollout_io layout");
+int np_f16_model_rollout(np_f16_ctx *ctx, int64_t n0, const np_f16_rollout_io *io, void *stream);
+/* The shape NP_ROLLOUT_AUTO resolves to for `rows` = n0 * fanout output rows on a device with num_cus CUs (solver 0 Euler / 1 rk4), or
+ * whether a pinned shape is honoured: *out = NP_ROLLOUT_THROUGHPUT / NP_ROLLOUT_SPLIT.  Host only, no device needed. */
+int np_f16_rollout_shape(int64_t rows, int32_t num_cus, int32_t solver, int32_t shape, int32_t *out);
+
 /* Average duration in ms of the `count` most recent np_f16_step / np_f16_combat_step launches on this context, measured with
  * HIP events on the launch stream: a start / stop pair attached to each kernel's own dispatch (hipExtLaunchKernelGGL — the
  * timestamps of the kernel's packet, no extra barrier packets between back-to-back launches; 0 disables, enable with

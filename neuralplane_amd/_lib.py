@@ -133,6 +133,26 @@ def dispatch_plan(n, num_cus, step=True, solver=0, tables=False, variant=0, gemm
     return {k: getattr(info, k) for k, _ in NpDispatchInfo._fields_ if k != 'reserved_'}
 
 
+class NpF16RolloutIo(C.Structure):   # include/neuralplane_amd.h: np_f16_rollout_io
+    _fields_ = [('s0', C.c_void_p), ('u0', C.c_void_p), ('ld0', C.c_int64),
+                ('actions', C.c_void_p), ('act_step_stride', C.c_int64), ('act_row_stride', C.c_int64),
+                ('horizon', C.c_int32), ('fanout', C.c_int32), ('record_every', C.c_int32), ('shape', C.c_int32),
+                ('s_out', C.c_void_p), ('u_out', C.c_void_p), ('ld_out', C.c_int64),
+                ('s_traj', C.c_void_p), ('traj_step_stride', C.c_int64)]
+
+
+ROLLOUT_SHAPES = {'auto': 0, 'throughput': 1, 'split': 2}   # NP_ROLLOUT_*
+
+
+def rollout_shape(rows, num_cus, solver=0, shape='auto'):
+    """np_f16_rollout_shape: the shape ('throughput' / 'split') a rollout of `rows` = n0 * fanout output rows takes on a device with num_cus
+    CUs (solver 0 Euler / 1 rk4), or RuntimeError when a pinned shape is refused.  No GPU needed."""
+    lib = load()
+    out = C.c_int32()
+    check(lib.np_f16_rollout_shape(int(rows), int(num_cus), int(solver), ROLLOUT_SHAPES[shape] if isinstance(shape, str) else int(shape), C.byref(out)))
+    return {v: k for k, v in ROLLOUT_SHAPES.items()}[out.value]
+
+
 def pack_kblob_gemm(blob):
     """np_f16_pack_kblob_gemm: the weight records of a context with aero_gemm_order as a list-like ctypes float array (host only, no GPU)."""
     lib = load()
@@ -150,7 +170,7 @@ def pack_kblob_gemm(blob):
 EXPORTS = ('np_abi_version', 'np_f16_airframe_default', 'np_f16_cache_floats', 'np_last_error', 'np_f16_ctx_create', 'np_f16_ctx_destroy', 'np_f16_reset',
            'np_f16_step', 'np_f16_derived', 'np_f16_aero_coefficients', 'np_f16_lowlevel_obs', 'np_f16_set_timing', 'np_f16_get_timing', 'np_f16_get_timing_samples', 'np_f16_set_trace', 'np_selfcheck_divc', 'np_selfcheck_math',
            'np_f16_combat_ctx_create', 'np_f16_combat_reset', 'np_f16_combat_step', 'np_f16_set_kernel_variant', 'np_actor_forward', 'np_rollout_returns', 'np_planning_inner_loop', 'np_planning_check', 'np_actor_pack_i8', 'np_rollout_insert', 'np_policy_act', 'np_planning_targets_obs', 'np_dispatch_plan', 'np_dispatch_plan_gemm', 'np_f16_pack_kblob_gemm',
-           'np_f16_set_fleet', 'np_f16_set_fleet_index')
+           'np_f16_set_fleet', 'np_f16_set_fleet_index', 'np_f16_model_rollout', 'np_f16_rollout_shape')
 KERNEL_VARIANTS = {'auto': 0, 'latency': 1, 'throughput': 2, 'pair': 3, 'latency8': 4, 'latency2': 5, 'latency4w': 6, 'dual8': 7, 'dual4': 8}
 
 _lib = None
@@ -197,6 +217,9 @@ def load():
     if hasattr(lib, 'np_f16_set_fleet'):   # (a measurement build loaded through NPF16_LIB may predate the fleet; the built library is checked against EXPORTS)
         lib.np_f16_set_fleet.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
         lib.np_f16_set_fleet_index.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+    if hasattr(lib, 'np_f16_model_rollout'):
+        lib.np_f16_model_rollout.argtypes = [C.c_void_p, C.c_int64, C.POINTER(NpF16RolloutIo), C.c_void_p]
+        lib.np_f16_rollout_shape.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
     lib.np_actor_forward.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_int, C.c_void_p]
     lib.np_planning_inner_loop.argtypes = [C.c_void_p, C.c_int64, C.POINTER(NpF16Io), C.POINTER(NpPlanningLoop), C.c_void_p]

@@ -435,6 +435,57 @@ class F16Batch:
         self.call_idx += 1
         self._version += 1
 
+    def rollout(self, actions, s=None, u=None, fanout=1, record_every=0, shape='auto', horizon=None):
+        """Open-loop look-ahead: H applications of F16Model.update (reference envs/models/F16_model.py:51-67) to an action sequence as ONE
+        launch (np_f16_model_rollout), bit-identical to H update() launches — and a pure function: the batch's state, flags, counters,
+        targets, call index and coefficient cache are left exactly as they were.
+        actions: [H, n0 * fanout, >=4], or [n0 * fanout, >=4] with horizon=H for one action held over all H steps.
+        s [12, n0], u [5, n0]: the start (both or neither); omitted = the batch's current state (n0 = n).  Output row r starts from start row
+        r // fanout and follows its own actions: K candidates per aircraft need no K copies of the state.
+        record_every = k > 0: also returns s_traj [H // k, 12, n0 * fanout], the states after steps k, 2k, ...
+        shape: 'auto' | 'throughput' | 'split' (_lib.rollout_shape; the same bits either way).
+        Returns (s_end [12, n0 * fanout], u_end [5, n0 * fanout][, s_traj])."""
+        if (s is None) != (u is None):
+            raise ValueError('rollout: s and u come together (or neither: the start is the batch\'s current state)')
+        if s is None:
+            s, u = self.s, self.u
+        if s.dim() != 2 or u.dim() != 2 or s.shape[0] != 12 or u.shape[0] != 5 or s.shape[1] != u.shape[1] or s.shape[1] < 1:
+            raise ValueError(f'rollout: s must be [12, n0] and u [5, n0], got {tuple(s.shape)} and {tuple(u.shape)}')
+        s = s.to(device=self.device, dtype=torch.float32).contiguous()
+        u = u.to(device=self.device, dtype=torch.float32).contiguous()
+        n0, fanout, record_every = int(s.shape[1]), int(fanout), int(record_every)
+        rows = n0 * max(fanout, 0)
+        actions = torch.as_tensor(actions).to(device=self.device, dtype=torch.float32)
+        if actions.dim() == 2:
+            if horizon is None:
+                raise ValueError('rollout: a held action [n0 * fanout, >=4] needs horizon=H')
+            held, h = True, int(horizon)
+        elif actions.dim() == 3:
+            if horizon is not None and int(horizon) != actions.shape[0]:
+                raise ValueError(f'rollout: horizon={horizon} but the action sequence has {actions.shape[0]} steps')
+            held, h = False, int(actions.shape[0])
+        else:
+            raise ValueError(f'rollout: actions must be [H, n0 * fanout, >=4] or [n0 * fanout, >=4], got {tuple(actions.shape)}')
+        if fanout >= 1 and (actions.shape[-2] != rows or actions.shape[-1] < 4):
+            raise ValueError(f'rollout: actions must have n0 * fanout = {rows} rows of >= 4 columns, got {tuple(actions.shape)}')
+        if actions.stride(-1) != 1 or (not held and h > 1 and actions.stride(0) < actions.stride(1) * (rows - 1) + 4):
+            actions = actions.contiguous()
+        io = _lib.NpF16RolloutIo()
+        io.s0, io.u0, io.ld0 = s.data_ptr(), u.data_ptr(), n0
+        io.actions, io.act_row_stride = actions.data_ptr(), actions.stride(-2)
+        io.act_step_stride = 0 if held or h <= 1 else actions.stride(0)
+        io.horizon, io.fanout, io.record_every, io.shape = h, fanout, record_every, _lib.ROLLOUT_SHAPES[shape]
+        rows_alloc = max(rows, 1)
+        s_end = torch.empty((12, rows_alloc), dtype=torch.float32, device=self.device)
+        u_end = torch.empty((5, rows_alloc), dtype=torch.float32, device=self.device)
+        io.s_out, io.u_out, io.ld_out = s_end.data_ptr(), u_end.data_ptr(), rows_alloc
+        s_traj = None
+        if record_every > 0:
+            s_traj = torch.empty((max(h, 0) // record_every, 12, rows_alloc), dtype=torch.float32, device=self.device)
+            io.s_traj, io.traj_step_stride = (s_traj.data_ptr() if s_traj.numel() else None), 12 * rows_alloc
+        _lib.check(self.lib.np_f16_model_rollout(self._ctx, n0, C.byref(io), self._stream()))
+        return (s_end, u_end) if s_traj is None else (s_end, u_end, s_traj)
+
     def model_reset(self, rand_u=None):
         """F16Model.reset(env) on its own (F16_model.py:33-45): state and controls of the rows the env has flagged are re-initialised
         (altitude and vt drawn) — the reset kernel on the env's flags; what BaseEnv.reset does beyond that (task.reset's targets, the step

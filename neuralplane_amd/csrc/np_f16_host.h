@@ -423,4 +423,56 @@ inline const char *dispatch_plan(int64_t n, int32_t num_cus, int32_t step, int32
     return nullptr;
 }
 
+// ---- np_f16_model_rollout (np_model_rollout.hip) -----------------------------------------------------------------------------------
+// Which shape a rollout of `rows` output rows takes: null and *out = NP_ROLLOUT_THROUGHPUT / NP_ROLLOUT_SPLIT, or the refusal.  The split
+// shape (eight waves per 64-row tile) is for grids that leave CUs idle under the throughput shape's 128-row workgroups of two waves: up to
+// ROLLOUT_SPLIT_ROWS_PER_CU rows per CU, i.e. while every 64-row tile has a CU of its own ("Open-loop model rollouts", has the
+// sweep behind the number).  Built for Euler only: an rk4 context takes the throughput shape at every size and refuses a pinned split.
+constexpr int64_t ROLLOUT_SPLIT_ROWS_PER_CU = 64;
+inline const char *rollout_shape(int64_t rows, int32_t num_cus, int32_t solver, int32_t pin, int32_t *out) {
+    if (!out) return "null argument";
+    if (rows <= 0 || num_cus <= 0) return "np_f16_rollout_shape: rows and num_cus must be positive";
+    if (solver != 0 && solver != 1) return "np_f16_rollout_shape: solver must be 0 (euler) or 1 (rk4)";
+    if (pin != NP_ROLLOUT_AUTO && pin != NP_ROLLOUT_THROUGHPUT && pin != NP_ROLLOUT_SPLIT)
+        return "np_f16_model_rollout: shape must be NP_ROLLOUT_AUTO, NP_ROLLOUT_THROUGHPUT or NP_ROLLOUT_SPLIT";
+    if (pin == NP_ROLLOUT_SPLIT && solver == 1)
+        return "np_f16_model_rollout: the split shape is built for Euler only (an rk4 context takes the throughput shape at every size)";
+    *out = pin != NP_ROLLOUT_AUTO ? pin : (solver == 0 && rows <= ROLLOUT_SPLIT_ROWS_PER_CU * num_cus) ? NP_ROLLOUT_SPLIT : NP_ROLLOUT_THROUGHPUT;
+    return nullptr;
+}
+
+// The record of a rollout of n0 start rows, checked before anything is launched: null, or the first thing wrong with it
+inline const char *rollout_io_error(int64_t n0, const np_f16_rollout_io *io) {
+    if (!io) return "np_f16_model_rollout: null io";
+    if (io->horizon < 1) return "np_f16_model_rollout: horizon must be at least 1";
+    if (io->fanout < 1) return "np_f16_model_rollout: fanout must be at least 1";
+    if (io->record_every < 0) return "np_f16_model_rollout: record_every must not be negative";
+    if (n0 < 1) return "np_f16_model_rollout: n0 must be at least 1";
+    if (!io->s0 || !io->u0) return "np_f16_model_rollout: null start state / controls (s0, u0)";
+    if (!io->actions) return "np_f16_model_rollout: null actions";
+    if (!io->s_out || !io->u_out) return "np_f16_model_rollout: null output state / controls (s_out, u_out)";
+    if (io->s_traj && io->record_every == 0) return "np_f16_model_rollout: s_traj without record_every";
+    const int64_t lim = 1ll << 30;   // 32-bit byte offsets inside a row-indexed array
+    if (n0 >= lim || io->fanout >= lim || n0 * io->fanout >= lim) return "np_f16_model_rollout: n0 * fanout must be below 2^30 rows";
+    const int64_t rows = n0 * io->fanout;
+    if (io->ld0 < n0 || io->ld0 >= lim) return "np_f16_model_rollout: ld0 must be at least n0 and below 2^30";
+    if (io->ld_out < rows || io->ld_out >= lim) return "np_f16_model_rollout: ld_out must be at least n0 * fanout and below 2^30";
+    if (io->act_row_stride < 4 || io->act_row_stride >= lim || rows * io->act_row_stride >= lim)
+        return "np_f16_model_rollout: act_row_stride must be at least 4 floats, and n0 * fanout * act_row_stride below 2^30";
+    if (io->act_step_stride != 0 && io->act_step_stride < (rows - 1) * io->act_row_stride + 4)
+        return "np_f16_model_rollout: act_step_stride must be 0 (one held action) or cover the n0 * fanout action rows of a step";
+    if (io->s_traj && io->traj_step_stride < 11 * io->ld_out + rows)
+        return "np_f16_model_rollout: traj_step_stride must cover one recorded state ([12][ld_out])";
+    return nullptr;
+}
+
+// Contexts the rollout kernel is not built for: null, or the refusal, by name
+inline const char *rollout_context_error(bool combat, bool fleet, bool gemm_order, bool tables) {
+    if (combat) return "np_f16_model_rollout: a SingleCombat context has no rollout kernel (create the context with np_f16_ctx_create)";
+    if (fleet) return "np_f16_model_rollout: a context with a fleet has no rollout kernel (it reads one airframe per context)";
+    if (gemm_order) return "np_f16_model_rollout: a context with aero_gemm_order has no rollout kernel (built for the default order of the aero nets)";
+    if (tables) return "np_f16_model_rollout: a context with aero_1d_tables has no rollout kernel (built for the MLP numerics)";
+    return nullptr;
+}
+
 }  // namespace npf16

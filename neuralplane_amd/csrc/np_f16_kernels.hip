@@ -29,6 +29,7 @@
 #include "np_rollout.h"
 #include "np_policy.h"
 #include "np_planning.h"
+#include "np_model_rollout.h"
 namespace npact8 {
 hipError_t launch_actor_i8(const float *weights, long long n, const float *obs, const float *h_in, const float *masks, float *actions, float *h_out,
                            hipStream_t stream);   // np_actor_i8.hip
@@ -1499,6 +1500,36 @@ int np_rollout_returns(int64_t T, int64_t N, double gamma, double gae_lambda, in
     else NP_RET(false, false);
 #undef NP_RET
     NP_HIP(hipGetLastError());
+    return 0;
+}
+
+int np_f16_rollout_shape(int64_t rows, int32_t num_cus, int32_t solver, int32_t shape, int32_t *out) {
+    if (const char *e = rollout_shape(rows, num_cus, solver, shape, out)) return fail(e);
+    return 0;
+}
+
+// H applications of F16Model.update in one launch (np_model_rollout.hip).  The record is checked first, then the context: nothing of either
+// is touched, and no device call is made, before every refusal has had its turn.
+static_assert(NP_ROLLOUT_THROUGHPUT == ROLLOUT_THROUGHPUT && NP_ROLLOUT_SPLIT == ROLLOUT_SPLIT, "np_model_rollout.h mirrors the NP_ROLLOUT_* numbers");
+int np_f16_model_rollout(np_f16_ctx *ctx, int64_t n0, const np_f16_rollout_io *io, void *stream) {
+    if (const char *e = rollout_io_error(n0, io)) return fail(e);
+    if (!ctx) return fail("np_f16_model_rollout: null ctx");
+    if (const char *e = rollout_context_error(ctx->combat, ctx->fleet_k > 0, ctx->gemm_order, !ctx->combat && ctx->cfg.aero_1d_tables != 0)) return fail(e);
+    int32_t shape = 0;
+    const int64_t rows = n0 * io->fanout;
+    if (const char *e = rollout_shape(rows, ctx->num_cus, ctx->solver, io->shape, &shape)) return fail(e);
+    DeviceGuard guard;
+    NP_HIP(guard.enter(ctx->device));
+    RolloutArgs a;
+    a.s0 = io->s0; a.u0 = io->u0; a.ld0 = io->ld0;
+    a.actions = io->actions; a.act_step_stride = io->act_step_stride; a.act_row_stride = io->act_row_stride;
+    a.s_out = io->s_out; a.u_out = io->u_out; a.ld_out = io->ld_out;
+    a.s_traj = io->record_every > 0 ? io->s_traj : nullptr; a.traj_step_stride = io->traj_step_stride;
+    a.rows = rows;
+    a.horizon = io->horizon; a.fanout = io->fanout; a.record_every = io->record_every; a.pad_ = 0;
+    a.cfg.dt = ctx->cfg.dt; a.cfg.pad_ = 0; a.cfg.af = ctx->cfg.af;
+    a.wt = ctx->wt;
+    NP_HIP(launch_model_rollout(ctx->solver, shape, a, (hipStream_t)stream));
     return 0;
 }
 

@@ -65,6 +65,19 @@ class F16Model(BaseModel):
         self.recent_s, self.recent_u = self.s.clone(), self.u.clone()
         self._b.update(torch.as_tensor(action, device=self._b.device))
 
+    def rollout(self, actions, s=None, u=None, fanout=1, record_every=0, shape='auto', horizon=None):
+        """Open-loop look-ahead: `for t in range(H): update(actions[t])` on a copy of the state, as ONE kernel launch (F16Batch.rollout,
+        np_f16_model_rollout) — bit-identical to H update() calls, and this model's s / u / recent_* are left exactly as they were.
+        actions [H, n * fanout, >=4] (or [n * fanout, >=4] with horizon=H: one held action); s [n0, 12] / u [n0, 5] default to the current
+        state; output row r starts from row r // fanout.  Returns (s_end [n * fanout, 12], u_end [n * fanout, 5][, s_traj [H // k, n * fanout, 12]])
+        in this class's row-major layout (views)."""
+        if s is not None:
+            s = torch.as_tensor(s, device=self._b.device).t()
+        if u is not None:
+            u = torch.as_tensor(u, device=self._b.device).t()
+        out = self._b.rollout(actions, s, u, fanout=fanout, record_every=record_every, shape=shape, horizon=horizon)
+        return (out[0].t(), out[1].t()) + ((out[2].transpose(1, 2),) if len(out) > 2 else ())
+
     def get_extended_state(self):
         """nlplant(hstack(s,u)) — reference returns [n,17] with zero control derivatives (F16_model.py:47-49)."""
         d = self._b.derived()
