@@ -548,6 +548,32 @@ int np_f16_model_rollout(np_f16_ctx *ctx, int64_t n0, const np_f16_rollout_io *i
  * whether a pinned shape is honoured: *out = NP_ROLLOUT_THROUGHPUT / NP_ROLLOUT_SPLIT.  Host only, no device needed. */
 int np_f16_rollout_shape(int64_t rows, int32_t num_cus, int32_t solver, int32_t shape, int32_t *out);
 
+/* Linearisation of the flight model (a new symbol and record within ABI 16; no earlier record changes): for each of n rows
+ *     xdot = f(s, u),   A = df/ds [12][12],   B = df/du [12][4]
+ * of F16Dynamics.nlplant (envs/models/F16/F16_dynamics.py:37-228) at the given (s, u) — s the 12 states, u the four lagged controls (T, el,
+ * ail, rud) nlplant reads — in ONE launch: the analytic Jacobian (forward mode through the 42 nets and the equations of motion), not finite
+ * differences.  A pure function: nothing of the context is written.  xdot is bit-identical to what the step kernels and the oracle compute;
+ * the derivative of the continuous-time f is the same for Euler and rk4 contexts (the discrete maps are the caller's).
+ *   arrays are planar, strides in floats: s0 [12][ld0], u0 [5][ld0] (row 4, lef, is not read); xdot [12][ld_out] (may be NULL);
+ *   A [144][ld_out], plane i * 12 + j = df_i/ds_j;  B [48][ld_out], plane i * 4 + j = df_i/du_j.  Every element of A and B is written
+ *   (the npos / epos columns are zero): the caller never clears them.
+ *   A row whose alpha, beta or el is not finite has NaN in rows 6..11 of A and B, as in its xdot.  Below the vt floor (0.01) the vt column is 0.
+ *   max_groups: 0 = the host rule picks the grid from the device's CU count (np_f16_linearize_groups); k > 0 caps it at k workgroups, each
+ *   walking several 64-row tiles.  The results do not depend on it.
+ * Everything is checked on the host before the launch (np_last_error names the field).  Refused by name: a context with a fleet, with
+ * aero_gemm_order, with aero_1d_tables, and a SingleCombat context.  cfg.airframe is honoured. */
+typedef struct np_f16_linearize_io {
+    const float *s0, *u0; int64_t ld0;          /* the flight condition: state [12][ld0], controls [5][ld0]; n rows */
+    float *xdot, *A, *B; int64_t ld_out;        /* [12][ld_out] or NULL, [144][ld_out], [48][ld_out] */
+    int32_t max_groups, reserved_;              /* 0 = auto; reserved_ must be 0 */
+} np_f16_linearize_io;
+NP_STATIC_ASSERT(sizeof(np_f16_linearize_io) == 64, "np_f16_linearize_io is 64 bytes");
+NP_STATIC_ASSERT(offsetof(np_f16_linearize_io, ld0) == 16 && offsetof(np_f16_linearize_io, xdot) == 24 && offsetof(np_f16_linearize_io, B) == 40, "np_f16_linearize_io layout");
+NP_STATIC_ASSERT(offsetof(np_f16_linearize_io, ld_out) == 48 && offsetof(np_f16_linearize_io, max_groups) == 56, "np_f16_linearize_io layout");
+int np_f16_model_linearize(np_f16_ctx *ctx, int64_t n, const np_f16_linearize_io *io, void *stream);
+/* The number of workgroups a linearisation of n rows launches on a device with num_cus CUs under max_groups.  Host only, no device needed. */
+int np_f16_linearize_groups(int64_t n, int32_t num_cus, int32_t max_groups, int32_t *out);
+
 /* Average duration in ms of the `count` most recent np_f16_step / np_f16_combat_step launches on this context, measured with
  * HIP events on the launch stream: a start / stop pair attached to each kernel's own dispatch (hipExtLaunchKernelGGL — the
  * timestamps of the kernel's packet, no extra barrier packets between back-to-back launches; 0 disables, enable with

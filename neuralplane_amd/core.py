@@ -486,6 +486,36 @@ class F16Batch:
         _lib.check(self.lib.np_f16_model_rollout(self._ctx, n0, C.byref(io), self._stream()))
         return (s_end, u_end) if s_traj is None else (s_end, u_end, s_traj)
 
+    def linearize(self, s=None, u=None, want_xdot=True, ld_out=None, max_groups=0):
+        """The flight model's linearisation about a flight condition, per row, as ONE launch (np_f16_model_linearize): xdot = f(s, u),
+        A = df/ds, B = df/du of F16Dynamics.nlplant — s the 12 states, u the four lagged controls (T, el, ail, rud).  The analytic Jacobian
+        (forward mode through the nets and the equations of motion); xdot is bit-identical to what the step kernels compute.  A pure
+        function: the batch is left exactly as it was.  With s and u omitted no torch kernel runs; a given s / u is converted to contiguous
+        fp32 on the device first (a torch copy unless it already is that).
+        s [12, n0], u [5, n0]: the flight condition (both or neither); omitted = the batch's current state.
+        Returns the planar buffers (xdot [12, n0] or None, A [12, 12, n0], B [12, 4, n0]) — A[i, j] = df_i/ds_j, B[i, j] = df_i/du_j, one row
+        of the batch per column — sliced out of [.., ld_out] allocations when ld_out > n0.  max_groups caps the grid (0 = auto)."""
+        if (s is None) != (u is None):
+            raise ValueError('linearize: s and u come together (or neither: the batch\'s current state)')
+        if s is None:
+            s, u = self.s, self.u
+        if s.dim() != 2 or u.dim() != 2 or s.shape[0] != 12 or u.shape[0] != 5 or s.shape[1] != u.shape[1] or s.shape[1] < 1:
+            raise ValueError(f'linearize: s must be [12, n0] and u [5, n0], got {tuple(s.shape)} and {tuple(u.shape)}')
+        s = s.to(device=self.device, dtype=torch.float32).contiguous()
+        u = u.to(device=self.device, dtype=torch.float32).contiguous()
+        n0 = int(s.shape[1])
+        ld = n0 if ld_out is None else int(ld_out)
+        ld_alloc = max(ld, 1)
+        io = _lib.NpF16LinearizeIo()
+        io.s0, io.u0, io.ld0 = s.data_ptr(), u.data_ptr(), n0
+        xdot = torch.empty((12, ld_alloc), dtype=torch.float32, device=self.device) if want_xdot else None
+        A = torch.empty((12, 12, ld_alloc), dtype=torch.float32, device=self.device)
+        B = torch.empty((12, 4, ld_alloc), dtype=torch.float32, device=self.device)
+        io.xdot, io.A, io.B, io.ld_out = (xdot.data_ptr() if want_xdot else None), A.data_ptr(), B.data_ptr(), ld
+        io.max_groups = int(max_groups)
+        _lib.check(self.lib.np_f16_model_linearize(self._ctx, n0, C.byref(io), self._stream()))
+        return (xdot[:, :n0] if want_xdot else None), A[:, :, :n0], B[:, :, :n0]
+
     def model_reset(self, rand_u=None):
         """F16Model.reset(env) on its own (F16_model.py:33-45): state and controls of the rows the env has flagged are re-initialised
         (altitude and vt drawn) — the reset kernel on the env's flags; what BaseEnv.reset does beyond that (task.reset's targets, the step

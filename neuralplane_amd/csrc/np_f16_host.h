@@ -475,4 +475,43 @@ inline const char *rollout_context_error(bool combat, bool fleet, bool gemm_orde
     return nullptr;
 }
 
+// ---- np_f16_model_linearize (np_model_linearize.hip) --------------------------------------------------------------------------------
+// The grid: one workgroup per 64-row tile up to LINEARIZE_GROUPS_PER_CU workgroup per CU (or max_groups, if given); beyond that a
+// workgroup walks the tiles g, g + groups, ... on one copy of the weight blob in its LDS.
+constexpr int64_t LINEARIZE_TILE = 64, LINEARIZE_GROUPS_PER_CU = 1;   // one 88 KB workgroup fits a CU
+inline const char *linearize_groups(int64_t n, int32_t num_cus, int32_t max_groups, int32_t *out) {
+    if (!out) return "null argument";
+    if (n < 1 || n >= (1ll << 30) || num_cus <= 0) return "np_f16_linearize_groups: n must be in [1, 2^30) and num_cus positive";
+    if (max_groups < 0) return "np_f16_model_linearize: max_groups must not be negative";
+    const int64_t tiles = (n + LINEARIZE_TILE - 1) / LINEARIZE_TILE;
+    const int64_t cap = max_groups > 0 ? (int64_t)max_groups : LINEARIZE_GROUPS_PER_CU * num_cus;
+    *out = (int32_t)(tiles < cap ? tiles : cap);
+    return nullptr;
+}
+
+// The record of a linearisation of n rows, checked before anything is launched: null, or the first thing wrong with it.  The kernel
+// addresses a row as (64-bit plane base) + (32-bit byte offset of the row): ld0 and ld_out below 2^30 keep the offset in range, and the
+// 192 planes of [xdot | A | B] are 64-bit arithmetic.
+inline const char *linearize_io_error(int64_t n, const np_f16_linearize_io *io) {
+    if (!io) return "np_f16_model_linearize: null io";
+    const int64_t lim = 1ll << 30;
+    if (n < 1 || n >= lim) return "np_f16_model_linearize: n must be at least 1 and below 2^30";
+    if (!io->s0 || !io->u0) return "np_f16_model_linearize: null flight condition (s0, u0)";
+    if (!io->A || !io->B) return "np_f16_model_linearize: null output (A, B)";
+    if (io->ld0 < n || io->ld0 >= lim) return "np_f16_model_linearize: ld0 must be at least n and below 2^30";
+    if (io->ld_out < n || io->ld_out >= lim) return "np_f16_model_linearize: ld_out must be at least n and below 2^30";
+    if (io->max_groups < 0) return "np_f16_model_linearize: max_groups must not be negative";
+    if (io->reserved_ != 0) return "np_f16_model_linearize: reserved_ must be 0";
+    return nullptr;
+}
+
+// Contexts the linearisation kernel is not built for: null, or the refusal, by name
+inline const char *linearize_context_error(bool combat, bool fleet, bool gemm_order, bool tables) {
+    if (combat) return "np_f16_model_linearize: a SingleCombat context has no linearisation kernel (create the context with np_f16_ctx_create)";
+    if (fleet) return "np_f16_model_linearize: a context with a fleet has no linearisation kernel (it reads one airframe per context)";
+    if (gemm_order) return "np_f16_model_linearize: a context with aero_gemm_order has no linearisation kernel (built for the default order of the aero nets)";
+    if (tables) return "np_f16_model_linearize: a context with aero_1d_tables has no linearisation kernel (built for the MLP numerics)";
+    return nullptr;
+}
+
 }  // namespace npf16

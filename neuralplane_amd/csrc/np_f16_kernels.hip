@@ -30,6 +30,7 @@
 #include "np_policy.h"
 #include "np_planning.h"
 #include "np_model_rollout.h"
+#include "np_model_linearize.h"
 namespace npact8 {
 hipError_t launch_actor_i8(const float *weights, long long n, const float *obs, const float *h_in, const float *masks, float *actions, float *h_out,
                            hipStream_t stream);   // np_actor_i8.hip
@@ -1530,6 +1531,32 @@ int np_f16_model_rollout(np_f16_ctx *ctx, int64_t n0, const np_f16_rollout_io *i
     a.cfg.dt = ctx->cfg.dt; a.cfg.pad_ = 0; a.cfg.af = ctx->cfg.af;
     a.wt = ctx->wt;
     NP_HIP(launch_model_rollout(ctx->solver, shape, a, (hipStream_t)stream));
+    return 0;
+}
+
+int np_f16_linearize_groups(int64_t n, int32_t num_cus, int32_t max_groups, int32_t *out) {
+    if (const char *e = linearize_groups(n, num_cus, max_groups, out)) return fail(e);
+    return 0;
+}
+
+// xdot, A = df/ds, B = df/du per row in one launch (np_model_linearize.hip).  As the rollout: the record first, then the context; nothing is
+// touched, and no device call is made, before every refusal has had its turn.
+static_assert(LINEARIZE_TILE == LIN_TILE && LINEARIZE_GROUPS_PER_CU == LIN_GROUPS_PER_CU, "np_f16_host.h mirrors np_model_linearize.h");
+int np_f16_model_linearize(np_f16_ctx *ctx, int64_t n, const np_f16_linearize_io *io, void *stream) {
+    if (const char *e = linearize_io_error(n, io)) return fail(e);
+    if (!ctx) return fail("np_f16_model_linearize: null ctx");
+    if (const char *e = linearize_context_error(ctx->combat, ctx->fleet_k > 0, ctx->gemm_order, !ctx->combat && ctx->cfg.aero_1d_tables != 0)) return fail(e);
+    int32_t groups = 0;
+    if (const char *e = linearize_groups(n, ctx->num_cus, io->max_groups, &groups)) return fail(e);
+    DeviceGuard guard;
+    NP_HIP(guard.enter(ctx->device));
+    LinearizeArgs a;
+    a.s0 = io->s0; a.u0 = io->u0; a.ld0 = io->ld0;
+    a.xdot = io->xdot; a.A = io->A; a.B = io->B; a.ld_out = io->ld_out;
+    a.rows = n;
+    a.kblob = ctx->wt.kblob;
+    a.af = ctx->cfg.af;
+    NP_HIP(launch_model_linearize(groups, a, (hipStream_t)stream));
     return 0;
 }
 

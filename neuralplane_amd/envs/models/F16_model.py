@@ -78,6 +78,19 @@ class F16Model(BaseModel):
         out = self._b.rollout(actions, s, u, fanout=fanout, record_every=record_every, shape=shape, horizon=horizon)
         return (out[0].t(), out[1].t()) + ((out[2].transpose(1, 2),) if len(out) > 2 else ())
 
+    def linearize(self, s=None, u=None, want_xdot=True):
+        """xdot = f(s, u), A = df/ds, B = df/du of the flight dynamics about a flight condition, per aircraft, as ONE kernel launch
+        (F16Batch.linearize, np_f16_model_linearize): what trim solvers, LQR / gain scheduling, iLQR and stability analysis start from.
+        s [n0, 12] / u [n0, 5] default to the current state; this model's s / u / recent_* are left exactly as they were.
+        Returns (xdot [n0, 12] or None, A [n0, 12, 12], B [n0, 12, 4]) — strided views of the planar buffers: the results are not copied.
+        With s and u omitted no torch kernel runs; a given s / u [n0, k] is transposed into the planar layout first (one torch copy each)."""
+        if s is not None:
+            s = torch.as_tensor(s, device=self._b.device).t()
+        if u is not None:
+            u = torch.as_tensor(u, device=self._b.device).t()
+        xdot, A, B = self._b.linearize(s, u, want_xdot=want_xdot)
+        return (xdot.t() if xdot is not None else None), A.permute(2, 0, 1), B.permute(2, 0, 1)
+
     def get_extended_state(self):
         """nlplant(hstack(s,u)) — reference returns [n,17] with zero control derivatives (F16_model.py:47-49)."""
         d = self._b.derived()
