@@ -574,6 +574,41 @@ int np_f16_model_linearize(np_f16_ctx *ctx, int64_t n, const np_f16_linearize_io
 /* The number of workgroups a linearisation of n rows launches on a device with num_cus CUs under max_groups.  Host only, no device needed. */
 int np_f16_linearize_groups(int64_t n, int32_t num_cus, int32_t max_groups, int32_t *out);
 
+/* The open-loop rollout differentiated (a new symbol and record within ABI 16; no earlier record changes): the vector-Jacobian product of
+ * `horizon` Euler applications of F16Model.update (envs/models/F16_model.py:51-67) with respect to the action sequence and the start, in ONE
+ * launch — what gradient shooting / gradient MPC, iLQR's backward sweep and back-propagation through time need.  With cotangents g_s_traj on
+ * the recorded states s_1..s_H and g_u_end on the controls after the last step it returns
+ *     g_s0 = dL/ds_0,  g_u0 = dL/du_0 (row 4, lef, is g_u_end's handed through),  g_actions[t] = dL/da_t
+ * about the states the rollout actually flew: s_traj is np_f16_model_rollout's with record_every = 1 for the same (s0, u0, actions, fanout);
+ * nothing is integrated again.  The clamp's gradient is torch's: it passes on [-1, 1], ends included, is 0 outside, and a NaN action gives NaN.
+ * A pure function: nothing of the context is written.
+ *   rows: n0 start rows, n0 * fanout output rows (output row r started from start row r / fanout).  g_s0 and g_u0 are PER OUTPUT ROW: the
+ *         caller sums the `fanout` candidates of a start row.
+ *   s_traj, g_s_traj: step t (the state after step t + 1) as [12][ld] at + t * traj_step_stride; g_u_end [5][ld] or NULL (zero).
+ *   g_actions: laid out as `actions` (same strides); four floats per row and step are written.  act_step_stride = 0 (a held action): ONE
+ *         gradient per row, the sum over the steps.
+ *   u_ws: workspace of horizon * 4 * ld floats (the kernel's forward pass of the control lag).
+ *   max_groups: as np_f16_linearize_io's (the grid is np_f16_linearize_groups of n0 * fanout rows).  The results do not depend on it.
+ *   A row whose alpha, beta or el is not finite at some step has NaN outputs, as its linearisation has; its neighbours are untouched.
+ * Everything is checked on the host before the launch (np_last_error names the field).  Refused by name: an rk4 context, a context with a
+ * fleet, with aero_gemm_order, with aero_1d_tables, and a SingleCombat context.  cfg.airframe is honoured. */
+typedef struct np_f16_rollout_vjp_io {
+    const float *s0, *u0; int64_t ld0;          /* start state [12][ld0], controls [5][ld0]; n0 rows */
+    const float *actions; int64_t act_step_stride, act_row_stride;   /* floats; step stride 0 = held */
+    int32_t horizon, fanout;
+    const float *s_traj, *g_s_traj; int64_t traj_step_stride, ld;     /* recorded states and their cotangents */
+    const float *g_u_end;                       /* [5][ld] or NULL */
+    float *g_s0, *g_u0; int64_t ld_out;         /* [12][ld_out], [5][ld_out] */
+    float *g_actions;                           /* as actions */
+    float *u_ws;                                /* horizon * 4 * ld floats */
+    int32_t max_groups, reserved_;              /* 0 = auto; reserved_ must be 0 */
+} np_f16_rollout_vjp_io;
+NP_STATIC_ASSERT(sizeof(np_f16_rollout_vjp_io) == 144, "np_f16_rollout_vjp_io is 144 bytes");
+NP_STATIC_ASSERT(offsetof(np_f16_rollout_vjp_io, actions) == 24 && offsetof(np_f16_rollout_vjp_io, horizon) == 48 && offsetof(np_f16_rollout_vjp_io, s_traj) == 56, "np_f16_rollout_vjp_io layout");
+NP_STATIC_ASSERT(offsetof(np_f16_rollout_vjp_io, ld) == 80 && offsetof(np_f16_rollout_vjp_io, g_u_end) == 88 && offsetof(np_f16_rollout_vjp_io, ld_out) == 112, "np_f16_rollout_vjp_io layout");
+NP_STATIC_ASSERT(offsetof(np_f16_rollout_vjp_io, g_actions) == 120 && offsetof(np_f16_rollout_vjp_io, u_ws) == 128 && offsetof(np_f16_rollout_vjp_io, max_groups) == 136, "np_f16_rollout_vjp_io layout");
+int np_f16_model_rollout_vjp(np_f16_ctx *ctx, int64_t n0, const np_f16_rollout_vjp_io *io, void *stream);
+
 /* Average duration in ms of the `count` most recent np_f16_step / np_f16_combat_step launches on this context, measured with
  * HIP events on the launch stream: a start / stop pair attached to each kernel's own dispatch (hipExtLaunchKernelGGL — the
  * timestamps of the kernel's packet, no extra barrier packets between back-to-back launches; 0 disables, enable with

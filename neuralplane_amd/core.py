@@ -141,6 +141,26 @@ def _check_fleet(sd, classes, index):
         raise ValueError('checkpoint was written with a different fleet (airframe_index: rows fly other classes) than this env has now')
 
 
+class _RolloutDiff(torch.autograd.Function):
+    """F16Batch.rollout_diff: forward = F16Batch.rollout(record_every=1), backward = one F16Batch.rollout_vjp launch"""
+
+    @staticmethod
+    def forward(ctx, batch, actions, s, u, fanout, horizon):
+        _, u_end, s_traj = batch.rollout(actions, s, u, fanout=fanout, record_every=1, horizon=horizon)
+        ctx.batch, ctx.fanout, ctx.horizon = batch, fanout, horizon
+        ctx.save_for_backward(actions, s, u, s_traj)
+        return s_traj, u_end
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_s_traj, g_u_end):
+        actions, s, u, s_traj = ctx.saved_tensors
+        g_s0, g_u0, g_a = ctx.batch.rollout_vjp(actions, s_traj, g_s_traj, g_u_end, s=s, u=u, fanout=ctx.fanout, horizon=ctx.horizon)
+        if actions.shape[-1] > 4:   # the columns F16Model.update does not read
+            g_a = torch.cat((g_a, torch.zeros_like(actions[..., 4:], dtype=torch.float32)), -1)
+        return None, g_a.to(actions.dtype), g_s0.to(s.dtype), g_u0.to(u.dtype), None, None
+
+
 class F16Batch:
     """N aircraft on one GPU.  `row0` is the global index of local row 0 (sharded batches).
     airframes / airframe_index: a fleet — K airframe classes and the class of every row (see set_fleet)."""
@@ -515,6 +535,71 @@ class F16Batch:
         io.max_groups = int(max_groups)
         _lib.check(self.lib.np_f16_model_linearize(self._ctx, n0, C.byref(io), self._stream()))
         return (xdot[:, :n0] if want_xdot else None), A[:, :, :n0], B[:, :, :n0]
+
+    def rollout_vjp(self, actions, s_traj, g_s_traj, g_u_end=None, s=None, u=None, fanout=1, horizon=None, max_groups=0, ld_out=None):
+        """The vector-Jacobian product of rollout(actions, s, u, fanout, record_every=1) as ONE launch (np_f16_model_rollout_vjp; Euler only):
+        with cotangents g_s_traj [H, 12, n0 * fanout] on the recorded states s_traj and g_u_end [5, n0 * fanout] (None = zero) on u_end,
+        returns (g_s0 [12, n0], g_u0 [5, n0], g_actions) — the gradients with respect to the start and to actions[..., :4] (same shape; a held
+        action [rows, >=4] gets the sum over the steps).  s_traj must be what rollout recorded for these very arguments: the kernel
+        linearises about it and integrates nothing again.  The clamp's gradient is torch's.  A pure function, as rollout.  max_groups caps the grid (0 = auto); g_s0 and
+        g_u0 are sliced out of [.., ld_out] allocations when ld_out > n0 * fanout."""
+        if (s is None) != (u is None):
+            raise ValueError('rollout_vjp: s and u come together (or neither: the start is the batch\'s current state)')
+        if s is None:
+            s, u = self.s, self.u
+        if s.dim() != 2 or u.dim() != 2 or s.shape[0] != 12 or u.shape[0] != 5 or s.shape[1] != u.shape[1] or s.shape[1] < 1:
+            raise ValueError(f'rollout_vjp: s must be [12, n0] and u [5, n0], got {tuple(s.shape)} and {tuple(u.shape)}')
+        f32 = dict(device=self.device, dtype=torch.float32)
+        s, u = s.to(**f32).contiguous(), u.to(**f32).contiguous()
+        n0, fanout = int(s.shape[1]), int(fanout)
+        rows = n0 * max(fanout, 0)
+        actions = torch.as_tensor(actions).to(**f32).contiguous()
+        if actions.dim() not in (2, 3) or (actions.dim() == 2 and horizon is None):
+            raise ValueError(f'rollout_vjp: actions must be [H, n0 * fanout, >=4], or [n0 * fanout, >=4] with horizon=H, got {tuple(actions.shape)}')
+        held, h = actions.dim() == 2, int(horizon if actions.dim() == 2 else actions.shape[0])
+        if horizon is not None and int(horizon) != h:
+            raise ValueError(f'rollout_vjp: horizon={horizon} but the action sequence has {h} steps')
+        if fanout >= 1 and (actions.shape[-2] != rows or actions.shape[-1] < 4):
+            raise ValueError(f'rollout_vjp: actions must have n0 * fanout = {rows} rows of >= 4 columns, got {tuple(actions.shape)}')
+        ld = max(rows, 1)
+        for name, x in (('s_traj', s_traj), ('g_s_traj', g_s_traj)):
+            if tuple(x.shape) != (h, 12, ld):
+                raise ValueError(f'rollout_vjp: {name} must be [H, 12, n0 * fanout] = {(h, 12, ld)}, got {tuple(x.shape)}')
+        if g_u_end is not None and tuple(g_u_end.shape) != (5, ld):
+            raise ValueError(f'rollout_vjp: g_u_end must be [5, n0 * fanout] = {(5, ld)}, got {tuple(g_u_end.shape)}')
+        s_traj, g_s_traj, g_u_end = s_traj.to(**f32), g_s_traj.to(**f32), (None if g_u_end is None else g_u_end.to(**f32))
+        ld_traj = s_traj.stride(1)   # slices [.., :rows] of [H, 12, ld] / [5, ld] buffers are taken as they are; anything else is copied
+        if (s_traj.stride(2) != 1 or ld_traj < ld or (h > 1 and s_traj.stride(0) < 12 * ld_traj) or g_s_traj.stride()[1:] != s_traj.stride()[1:]
+                or (h > 1 and g_s_traj.stride(0) != s_traj.stride(0))
+                or (g_u_end is not None and g_u_end.stride() != (ld_traj, 1))):
+            s_traj, g_s_traj, g_u_end, ld_traj = s_traj.contiguous(), g_s_traj.contiguous(), (None if g_u_end is None else g_u_end.contiguous()), ld
+        ld_out = ld if ld_out is None else int(ld_out)
+        io = _lib.NpF16RolloutVjpIo()
+        io.s0, io.u0, io.ld0 = s.data_ptr(), u.data_ptr(), n0
+        io.actions, io.act_row_stride, io.act_step_stride = actions.data_ptr(), actions.stride(-2), (0 if held or h <= 1 else actions.stride(0))
+        io.horizon, io.fanout, io.max_groups = h, fanout, int(max_groups)
+        io.s_traj, io.g_s_traj, io.traj_step_stride, io.ld = s_traj.data_ptr(), g_s_traj.data_ptr(), (s_traj.stride(0) if h > 1 else 12 * ld_traj), ld_traj   # (a size-1 dimension's stride is arbitrary)
+        io.g_u_end = None if g_u_end is None else g_u_end.data_ptr()
+        g_s0 = torch.empty((12, max(ld_out, 1)), **f32)
+        g_u0 = torch.empty((5, max(ld_out, 1)), **f32)
+        g_act = torch.empty_like(actions) if actions.shape[-1] == 4 else torch.zeros_like(actions)   # the kernel writes four columns
+        u_ws = torch.empty((max(h, 1), 4, ld_traj), **f32)
+        io.g_s0, io.g_u0, io.ld_out, io.g_actions, io.u_ws = g_s0.data_ptr(), g_u0.data_ptr(), ld_out, g_act.data_ptr(), u_ws.data_ptr()
+        _lib.check(self.lib.np_f16_model_rollout_vjp(self._ctx, n0, C.byref(io), self._stream()))
+        g_s0, g_u0 = g_s0[:, :ld], g_u0[:, :ld]
+        if fanout > 1:   # per output row -> per start row: one sum over the K candidates
+            g_s0, g_u0 = g_s0.reshape(12, n0, fanout).sum(-1), g_u0.reshape(5, n0, fanout).sum(-1)
+        return g_s0, g_u0, g_act[..., :4]
+
+    def rollout_diff(self, actions, s=None, u=None, fanout=1, horizon=None):
+        """rollout(record_every=1) that loss.backward() works through: returns (s_traj [H, 12, n0 * fanout], u_end [5, n0 * fanout]), the
+        forward pass the very rollout launch (bit-identical), the backward pass ONE rollout_vjp launch.  Differentiable with respect to
+        actions, s and u (Euler contexts)."""
+        if (s is None) != (u is None):
+            raise ValueError('rollout_diff: s and u come together (or neither: the start is the batch\'s current state)')
+        if s is None:   # a copy: the step kernels write self.s / self.u in place, and backward() must see the start s_traj was flown from
+            s, u = self.s.clone(), self.u.clone()
+        return _RolloutDiff.apply(self, torch.as_tensor(actions, device=self.device), s, u, int(fanout), horizon)
 
     def model_reset(self, rand_u=None):
         """F16Model.reset(env) on its own (F16_model.py:33-45): state and controls of the rows the env has flagged are re-initialised

@@ -514,4 +514,43 @@ inline const char *linearize_context_error(bool combat, bool fleet, bool gemm_or
     return nullptr;
 }
 
+// ---- np_f16_model_rollout_vjp (np_model_rollout_vjp.hip) ----------------------------------------------------------------------------
+// The record of a reverse sweep over n0 start rows, checked before anything is launched: null, or the first thing wrong with it.  The
+// limits are the rollout's (rows of every array are a 64-bit base + a 32-bit byte offset); the grid is linearize_groups of n0 * fanout rows.
+inline const char *rollout_vjp_io_error(int64_t n0, const np_f16_rollout_vjp_io *io) {
+    if (!io) return "np_f16_model_rollout_vjp: null io";
+    if (io->horizon < 1) return "np_f16_model_rollout_vjp: horizon must be at least 1";
+    if (io->fanout < 1) return "np_f16_model_rollout_vjp: fanout must be at least 1";
+    if (n0 < 1) return "np_f16_model_rollout_vjp: n0 must be at least 1";
+    if (!io->s0 || !io->u0) return "np_f16_model_rollout_vjp: null start state / controls (s0, u0)";
+    if (!io->actions) return "np_f16_model_rollout_vjp: null actions";
+    if (!io->s_traj || !io->g_s_traj) return "np_f16_model_rollout_vjp: null recorded states / cotangents (s_traj, g_s_traj)";
+    if (!io->g_s0 || !io->g_u0 || !io->g_actions) return "np_f16_model_rollout_vjp: null output (g_s0, g_u0, g_actions)";
+    if (!io->u_ws) return "np_f16_model_rollout_vjp: null workspace (u_ws)";
+    const int64_t lim = 1ll << 30;   // 32-bit byte offsets inside a row-indexed array
+    if (n0 >= lim || io->fanout >= lim || n0 * io->fanout >= lim) return "np_f16_model_rollout_vjp: n0 * fanout must be below 2^30 rows";
+    const int64_t rows = n0 * io->fanout;
+    if (io->ld0 < n0 || io->ld0 >= lim) return "np_f16_model_rollout_vjp: ld0 must be at least n0 and below 2^30";
+    if (io->ld < rows || io->ld >= lim) return "np_f16_model_rollout_vjp: ld must be at least n0 * fanout and below 2^30";
+    if (io->ld_out < rows || io->ld_out >= lim) return "np_f16_model_rollout_vjp: ld_out must be at least n0 * fanout and below 2^30";
+    if (io->act_row_stride < 4 || io->act_row_stride >= lim || rows * io->act_row_stride >= lim)
+        return "np_f16_model_rollout_vjp: act_row_stride must be at least 4 floats, and n0 * fanout * act_row_stride below 2^30";
+    if (io->act_step_stride != 0 && io->act_step_stride < (rows - 1) * io->act_row_stride + 4)
+        return "np_f16_model_rollout_vjp: act_step_stride must be 0 (one held action) or cover the n0 * fanout action rows of a step";
+    if (io->traj_step_stride < 11 * io->ld + rows) return "np_f16_model_rollout_vjp: traj_step_stride must cover one recorded state ([12][ld])";
+    if (io->max_groups < 0) return "np_f16_model_rollout_vjp: max_groups must not be negative";
+    if (io->reserved_ != 0) return "np_f16_model_rollout_vjp: reserved_ must be 0";
+    return nullptr;
+}
+
+// Contexts the reverse sweep is not built for: null, or the refusal, by name
+inline const char *rollout_vjp_context_error(bool combat, bool fleet, bool gemm_order, bool tables, int32_t solver) {
+    if (combat) return "np_f16_model_rollout_vjp: a SingleCombat context has no rollout kernels (create the context with np_f16_ctx_create)";
+    if (fleet) return "np_f16_model_rollout_vjp: a context with a fleet has no reverse sweep (it reads one airframe per context)";
+    if (gemm_order) return "np_f16_model_rollout_vjp: a context with aero_gemm_order has no reverse sweep (built for the default order of the aero nets)";
+    if (tables) return "np_f16_model_rollout_vjp: a context with aero_1d_tables has no reverse sweep (built for the MLP numerics)";
+    if (solver != 0) return "np_f16_model_rollout_vjp: solver: rk4 has no reverse sweep (built for the Euler step)";
+    return nullptr;
+}
+
 }  // namespace npf16

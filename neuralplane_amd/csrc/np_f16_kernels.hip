@@ -31,6 +31,7 @@
 #include "np_planning.h"
 #include "np_model_rollout.h"
 #include "np_model_linearize.h"
+#include "np_model_rollout_vjp.h"
 namespace npact8 {
 hipError_t launch_actor_i8(const float *weights, long long n, const float *obs, const float *h_in, const float *masks, float *actions, float *h_out,
                            hipStream_t stream);   // np_actor_i8.hip
@@ -1557,6 +1558,32 @@ int np_f16_model_linearize(np_f16_ctx *ctx, int64_t n, const np_f16_linearize_io
     a.kblob = ctx->wt.kblob;
     a.af = ctx->cfg.af;
     NP_HIP(launch_model_linearize(groups, a, (hipStream_t)stream));
+    return 0;
+}
+
+// The rollout's vector-Jacobian product in one launch (np_model_rollout_vjp.hip).  As its siblings: the record first, then the context;
+// nothing is touched, and no device call is made, before every refusal has had its turn.
+int np_f16_model_rollout_vjp(np_f16_ctx *ctx, int64_t n0, const np_f16_rollout_vjp_io *io, void *stream) {
+    if (const char *e = rollout_vjp_io_error(n0, io)) return fail(e);
+    if (!ctx) return fail("np_f16_model_rollout_vjp: null ctx");
+    if (const char *e = rollout_vjp_context_error(ctx->combat, ctx->fleet_k > 0, ctx->gemm_order, !ctx->combat && ctx->cfg.aero_1d_tables != 0, ctx->solver)) return fail(e);
+    const int64_t rows = n0 * io->fanout;
+    int32_t groups = 0;
+    if (const char *e = linearize_groups(rows, ctx->num_cus, io->max_groups, &groups)) return fail(e);
+    DeviceGuard guard;
+    NP_HIP(guard.enter(ctx->device));
+    RolloutVjpArgs a;
+    a.s0 = io->s0; a.u0 = io->u0; a.ld0 = io->ld0;
+    a.actions = io->actions; a.act_step_stride = io->act_step_stride; a.act_row_stride = io->act_row_stride;
+    a.s_traj = io->s_traj; a.g_s_traj = io->g_s_traj; a.traj_step_stride = io->traj_step_stride;
+    a.g_u_end = io->g_u_end;
+    a.g_s0 = io->g_s0; a.g_u0 = io->g_u0; a.g_actions = io->g_actions; a.u_ws = io->u_ws;
+    a.ld_traj = io->ld; a.ld_out = io->ld_out;
+    a.rows = rows;
+    a.horizon = io->horizon; a.fanout = io->fanout; a.dt = ctx->cfg.dt; a.pad_ = 0;
+    a.kblob = ctx->wt.kblob;
+    a.af = ctx->cfg.af;
+    NP_HIP(launch_model_rollout_vjp(groups, a, (hipStream_t)stream));
     return 0;
 }
 

@@ -78,6 +78,17 @@ class F16Model(BaseModel):
         out = self._b.rollout(actions, s, u, fanout=fanout, record_every=record_every, shape=shape, horizon=horizon)
         return (out[0].t(), out[1].t()) + ((out[2].transpose(1, 2),) if len(out) > 2 else ())
 
+    def rollout_diff(self, actions, s=None, u=None, fanout=1, horizon=None):
+        """rollout(record_every=1) that loss.backward() works through (F16Batch.rollout_diff: the backward pass is ONE launch,
+        np_f16_model_rollout_vjp; Euler only): differentiable with respect to actions, s [n0, 12] and u [n0, 5].
+        Returns (s_traj [H, n * fanout, 12], u_end [n * fanout, 5]) in this class's row-major layout (views)."""
+        if s is not None:
+            s = torch.as_tensor(s, device=self._b.device).t()
+        if u is not None:
+            u = torch.as_tensor(u, device=self._b.device).t()
+        s_traj, u_end = self._b.rollout_diff(actions, s, u, fanout=fanout, horizon=horizon)
+        return s_traj.transpose(1, 2), u_end.t()
+
     def linearize(self, s=None, u=None, want_xdot=True):
         """xdot = f(s, u), A = df/ds, B = df/du of the flight dynamics about a flight condition, per aircraft, as ONE kernel launch
         (F16Batch.linearize, np_f16_model_linearize): what trim solvers, LQR / gain scheduling, iLQR and stability analysis start from.
