@@ -609,6 +609,50 @@ NP_STATIC_ASSERT(offsetof(np_f16_rollout_vjp_io, ld) == 80 && offsetof(np_f16_ro
 NP_STATIC_ASSERT(offsetof(np_f16_rollout_vjp_io, g_actions) == 120 && offsetof(np_f16_rollout_vjp_io, u_ws) == 128 && offsetof(np_f16_rollout_vjp_io, max_groups) == 136, "np_f16_rollout_vjp_io layout");
 int np_f16_model_rollout_vjp(np_f16_ctx *ctx, int64_t n0, const np_f16_rollout_vjp_io *io, void *stream);
 
+/* iLQR's backward pass on the flight model (a new symbol and record within ABI 16; no earlier record changes): the Riccati sweep over
+ * `horizon` Euler applications of F16Model.update (envs/models/F16_model.py:51-67), per row and in ONE launch.  With x = (s[12], u[0:4]), the
+ * step's Jacobian Phi = [[I + dt A, dt B], [0, I]] in (s, u') coordinates about the states the rollout recorded (s_traj as for
+ * np_f16_model_rollout_vjp), kappa and gain_k the control lag's factors, D = diag(gain_k 1[-1 <= a_k <= 1]) and S = diag(1 x 12, kappa x 4),
+ * the sweep runs t = horizon - 1 .. 0 from p = (0, g_u_end), P = 0:
+ *     p_s += g_s_traj[t];  P_ss += diag(h_s[t]);  w = Phi^T p;  W = Phi^T P Phi
+ *     Q_x = S w;  Q_a = D w_u + g_actions_in[t];  Q_xx = S W S;  Q_ax = D [W_us, kappa W_uu];  Q_aa = D W_uu D + diag(h_a);  Qt = Q_aa + mu I
+ *     k_t = -Qt^-1 Q_a;  K_t = -Qt^-1 Q_ax;  dV += (k^T Q_a, 1/2 k^T Q_aa k)
+ *     p <- Q_x + K^T Q_aa k + K^T Q_a + Q_ax^T k;  P <- Q_xx + K^T Q_aa K + K^T Q_ax + Q_ax^T K, symmetrised
+ * so that a_t = abar_t + alpha k_t + K_t (x_t - xbar_t) is the iLQR step.  A pure function: nothing of the context is written.
+ *   cost model: g_s_traj = d cost / d s_{t+1} (as np_f16_rollout_vjp_io's), g_actions_in [horizon][4][ld] the direct d cost / d a_t,
+ *         g_u_end [4][ld] or NULL; h_s [horizon][12] (HOST memory: checked here, then copied to h_ws on the stream) and h_a[4] the
+ *         Gauss-Newton diagonal Hessians, shared by the rows; mu the regularisation, or mu_rows [n0 * fanout] (device) per row.
+ *   outputs, planar: k [horizon][4][ld_out], K [horizon][64][ld_out] (plane 16 a + j = K_t[a][j]), dV [2][ld_out], status [n0 * fanout],
+ *         and, if asked for (both or neither), p0 [16][ld_out] and P0 [256][ld_out] (plane 16 i + j): the value gradient / Hessian at x_0.
+ *   status: -1, or the step t at which the row STOPPED — a pivot of Qt not positive or not finite, or Q_a not finite (a non-finite cost
+ *         gradient).  Its k, K of steps t .. 0, its dV, p0 and P0 are 0; its neighbours are untouched.  Raise mu for it and sweep again.
+ *   A row whose alpha, beta or el is not finite at step t, or with a NaN action there, has NaN in k, K of steps t .. 0, dV, p0 and P0,
+ *         as its linearisation has (status -1); its neighbours are untouched.
+ *   workspaces: u_ws horizon * 4 * ld floats, p_ws n0 * fanout * 256 floats, h_ws horizon * 12 floats.
+ *   rows, actions, max_groups: as np_f16_rollout_vjp_io's (a held action has no sweep: act_step_stride covers a step's rows).
+ * Everything is checked on the host before the launch (np_last_error names the field): h_a[k] + mu must be positive, h_s finite and not
+ * negative.  Refused by name: an rk4 context, a context with a fleet, with aero_gemm_order, with aero_1d_tables, and a SingleCombat context. */
+typedef struct np_f16_ilqr_io {
+    const float *s0, *u0; int64_t ld0;          /* start state [12][ld0], controls [5][ld0]; n0 rows */
+    const float *actions; int64_t act_step_stride, act_row_stride;   /* floats */
+    int32_t horizon, fanout;
+    const float *s_traj, *g_s_traj; int64_t traj_step_stride, ld;     /* recorded states and the cost's gradients on them */
+    const float *g_actions_in, *g_u_end;        /* [horizon][4][ld]; [4][ld] or NULL */
+    const float *h_s;                           /* HOST [horizon][12] */
+    float h_a[4];
+    float mu; int32_t max_groups;               /* max_groups: 0 = auto */
+    const float *mu_rows;                       /* device [n0 * fanout] or NULL (mu for every row) */
+    float *k, *K, *dV; int32_t *status;         /* [horizon][4][ld_out], [horizon][64][ld_out], [2][ld_out], [n0 * fanout] */
+    float *p0, *P0; int64_t ld_out;             /* [16][ld_out], [256][ld_out], or both NULL */
+    float *u_ws, *p_ws, *h_ws;                  /* horizon * 4 * ld, n0 * fanout * 256, horizon * 12 floats */
+} np_f16_ilqr_io;
+NP_STATIC_ASSERT(sizeof(np_f16_ilqr_io) == 224, "np_f16_ilqr_io is 224 bytes");
+NP_STATIC_ASSERT(offsetof(np_f16_ilqr_io, actions) == 24 && offsetof(np_f16_ilqr_io, horizon) == 48 && offsetof(np_f16_ilqr_io, s_traj) == 56, "np_f16_ilqr_io layout");
+NP_STATIC_ASSERT(offsetof(np_f16_ilqr_io, g_actions_in) == 88 && offsetof(np_f16_ilqr_io, h_s) == 104 && offsetof(np_f16_ilqr_io, h_a) == 112, "np_f16_ilqr_io layout");
+NP_STATIC_ASSERT(offsetof(np_f16_ilqr_io, mu) == 128 && offsetof(np_f16_ilqr_io, mu_rows) == 136 && offsetof(np_f16_ilqr_io, k) == 144, "np_f16_ilqr_io layout");
+NP_STATIC_ASSERT(offsetof(np_f16_ilqr_io, status) == 168 && offsetof(np_f16_ilqr_io, ld_out) == 192 && offsetof(np_f16_ilqr_io, h_ws) == 216, "np_f16_ilqr_io layout");
+int np_f16_model_ilqr_backward(np_f16_ctx *ctx, int64_t n0, const np_f16_ilqr_io *io, void *stream);
+
 /* Average duration in ms of the `count` most recent np_f16_step / np_f16_combat_step launches on this context, measured with
  * HIP events on the launch stream: a start / stop pair attached to each kernel's own dispatch (hipExtLaunchKernelGGL — the
  * timestamps of the kernel's packet, no extra barrier packets between back-to-back launches; 0 disables, enable with

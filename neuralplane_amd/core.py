@@ -591,6 +591,69 @@ class F16Batch:
             g_s0, g_u0 = g_s0.reshape(12, n0, fanout).sum(-1), g_u0.reshape(5, n0, fanout).sum(-1)
         return g_s0, g_u0, g_act[..., :4]
 
+    def ilqr_backward(self, actions, s_traj, g_s_traj, g_actions, h_s, h_a, mu, g_u_end=None, s=None, u=None, fanout=1, want_value=False,
+                      max_groups=0, ld_out=None):
+        """iLQR's backward pass about rollout(actions, s, u, fanout, record_every=1) as ONE launch (np_f16_model_ilqr_backward; Euler only): the
+        Riccati sweep over the step Jacobians in x = (s[12], u[0:4]), with the cost given by its gradients g_s_traj [H, 12, rows] (on the recorded
+        states s_traj), g_actions [H, 4, rows] (the direct d cost / d a_t, planar) and g_u_end [4, rows] (None = zero), and by its Gauss-Newton
+        diagonals h_s [H, 12] and h_a [4], shared by the rows (host values: they are checked before the launch).  mu: the regularisation, a
+        number or a [rows] tensor (per row, on the device).  rows = n0 * fanout.
+        Returns (k [H, 4, rows], K [H, 4, 16, rows], dV [2, rows], status [rows] int32[, p0 [16, rows], P0 [16, 16, rows]]): the step is
+        a_t = abar_t + alpha k_t + K_t (x_t - xbar_t); dV = (sum k^T Q_a, sum 1/2 k^T Q_aa k), the expected cost change being
+        alpha dV[0] + alpha^2 dV[1]; status -1, or the step at which the row stopped (a failed pivot or a non-finite cost gradient: its
+        outputs from there down are 0 — raise mu for it and sweep again).  A pure function, as rollout.  max_groups caps the grid (0 = auto);
+        the outputs are sliced out of [.., ld_out] allocations when ld_out > rows."""
+        if (s is None) != (u is None):
+            raise ValueError('ilqr_backward: s and u come together (or neither: the start is the batch\'s current state)')
+        if s is None:
+            s, u = self.s, self.u
+        if s.dim() != 2 or u.dim() != 2 or s.shape[0] != 12 or u.shape[0] != 5 or s.shape[1] != u.shape[1] or s.shape[1] < 1:
+            raise ValueError(f'ilqr_backward: s must be [12, n0] and u [5, n0], got {tuple(s.shape)} and {tuple(u.shape)}')
+        f32 = dict(device=self.device, dtype=torch.float32)
+        s, u = s.to(**f32).contiguous(), u.to(**f32).contiguous()
+        n0, fanout = int(s.shape[1]), int(fanout)
+        rows = n0 * max(fanout, 0)
+        actions = torch.as_tensor(actions).to(**f32).contiguous()
+        if actions.dim() != 3 or (fanout >= 1 and (actions.shape[1] != rows or actions.shape[2] < 4)):
+            raise ValueError(f'ilqr_backward: actions must be [H, n0 * fanout = {rows}, >=4], got {tuple(actions.shape)}')
+        h, ld = int(actions.shape[0]), max(rows, 1)
+        planar = [('s_traj', s_traj, (h, 12, ld)), ('g_s_traj', g_s_traj, (h, 12, ld)), ('g_actions', g_actions, (h, 4, ld))]
+        planar += [('g_u_end', g_u_end, (4, ld))] if g_u_end is not None else []
+        for name, x, shape in planar:
+            if tuple(x.shape) != shape:
+                raise ValueError(f'ilqr_backward: {name} must be {shape}, got {tuple(x.shape)}')
+        s_traj, g_s_traj, g_actions = (x.to(**f32).contiguous() for x in (s_traj, g_s_traj, g_actions))
+        g_u_end = None if g_u_end is None else g_u_end.to(**f32).contiguous()
+        h_s = torch.as_tensor(h_s).to(device='cpu', dtype=torch.float32).contiguous()
+        h_a = [float(x) for x in torch.as_tensor(h_a).reshape(-1).tolist()]
+        if tuple(h_s.shape) != (h, 12) or len(h_a) != 4:
+            raise ValueError(f'ilqr_backward: h_s must be [H, 12] = {(h, 12)} and h_a [4], got {tuple(h_s.shape)} and {len(h_a)} values')
+        mu_rows = None
+        if torch.is_tensor(mu) and mu.dim() > 0:
+            if tuple(mu.shape) != (ld,):
+                raise ValueError(f'ilqr_backward: a per-row mu must be [n0 * fanout] = {(ld,)}, got {tuple(mu.shape)}')
+            mu_rows, mu = mu.to(**f32).contiguous(), 0.0
+        ld_out = ld if ld_out is None else int(ld_out)
+        lo = max(ld_out, 1)
+        io = _lib.NpF16IlqrIo()
+        io.s0, io.u0, io.ld0 = s.data_ptr(), u.data_ptr(), n0
+        io.actions, io.act_row_stride, io.act_step_stride = actions.data_ptr(), actions.stride(1), actions.stride(0) if h > 1 else 0
+        io.horizon, io.fanout, io.max_groups = h, fanout, int(max_groups)
+        io.s_traj, io.g_s_traj, io.traj_step_stride, io.ld = s_traj.data_ptr(), g_s_traj.data_ptr(), 12 * ld, ld
+        io.g_actions_in, io.g_u_end = g_actions.data_ptr(), (None if g_u_end is None else g_u_end.data_ptr())
+        io.h_s, io.h_a, io.mu = h_s.data_ptr(), (C.c_float * 4)(*h_a), float(mu)
+        io.mu_rows = None if mu_rows is None else mu_rows.data_ptr()
+        k, K, dV = (torch.empty(shape + (lo,), **f32) for shape in ((h, 4), (h, 64), (2,)))
+        status = torch.empty(ld, dtype=torch.int32, device=self.device)
+        p0, P0 = (torch.empty((16, lo), **f32), torch.empty((256, lo), **f32)) if want_value else (None, None)
+        u_ws, p_ws, h_ws = torch.empty((h, 4, ld), **f32), torch.empty((ld, 256), **f32), torch.empty((h, 12), **f32)
+        io.k, io.K, io.dV, io.status, io.ld_out = k.data_ptr(), K.data_ptr(), dV.data_ptr(), status.data_ptr(), ld_out
+        io.p0, io.P0 = (p0.data_ptr(), P0.data_ptr()) if want_value else (None, None)
+        io.u_ws, io.p_ws, io.h_ws = u_ws.data_ptr(), p_ws.data_ptr(), h_ws.data_ptr()
+        _lib.check(self.lib.np_f16_model_ilqr_backward(self._ctx, n0, C.byref(io), self._stream()))
+        out = (k[..., :ld], K.view(h, 4, 16, lo)[..., :ld], dV[:, :ld], status)
+        return out + ((p0[:, :ld], P0.view(16, 16, lo)[..., :ld]) if want_value else ())
+
     def rollout_diff(self, actions, s=None, u=None, fanout=1, horizon=None):
         """rollout(record_every=1) that loss.backward() works through: returns (s_traj [H, 12, n0 * fanout], u_end [5, n0 * fanout]), the
         forward pass the very rollout launch (bit-identical), the backward pass ONE rollout_vjp launch.  Differentiable with respect to

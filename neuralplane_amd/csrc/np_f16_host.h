@@ -553,4 +553,52 @@ inline const char *rollout_vjp_context_error(bool combat, bool fleet, bool gemm_
     return nullptr;
 }
 
+// ---- np_f16_model_ilqr_backward (np_model_ilqr.hip) ----------------------------------------------------------------------------------
+// The record of a Riccati sweep over n0 start rows, checked before anything is launched: null, or the first thing wrong with it.  The
+// limits are the reverse sweep's; the grid is linearize_groups of n0 * fanout rows.  h_s is HOST memory and is read here: the Gauss-Newton
+// diagonals must be finite and not negative, and h_a[k] + mu positive (a per-row mu_rows is device memory: a row whose h_a + mu_rows is
+// not positive ends in a failed pivot, status[row] = horizon - 1).
+inline const char *ilqr_io_error(int64_t n0, const np_f16_ilqr_io *io) {
+    if (!io) return "np_f16_model_ilqr_backward: null io";
+    if (io->horizon < 1) return "np_f16_model_ilqr_backward: horizon must be at least 1";
+    if (io->fanout < 1) return "np_f16_model_ilqr_backward: fanout must be at least 1";
+    if (n0 < 1) return "np_f16_model_ilqr_backward: n0 must be at least 1";
+    if (!io->s0 || !io->u0) return "np_f16_model_ilqr_backward: null start state / controls (s0, u0)";
+    if (!io->actions) return "np_f16_model_ilqr_backward: null actions";
+    if (!io->s_traj || !io->g_s_traj) return "np_f16_model_ilqr_backward: null recorded states / cost gradients (s_traj, g_s_traj)";
+    if (!io->g_actions_in) return "np_f16_model_ilqr_backward: null action cost gradients (g_actions_in)";
+    if (!io->h_s) return "np_f16_model_ilqr_backward: null state cost Hessian diagonal (h_s, host memory)";
+    if (!io->k || !io->K || !io->dV || !io->status) return "np_f16_model_ilqr_backward: null output (k, K, dV, status)";
+    if ((io->p0 == nullptr) != (io->P0 == nullptr)) return "np_f16_model_ilqr_backward: p0 and P0 come together (or neither)";
+    if (!io->u_ws || !io->p_ws || !io->h_ws) return "np_f16_model_ilqr_backward: null workspace (u_ws, p_ws, h_ws)";
+    const int64_t lim = 1ll << 30;   // 32-bit byte offsets inside a row-indexed array
+    if (n0 >= lim || io->fanout >= lim || n0 * io->fanout >= lim) return "np_f16_model_ilqr_backward: n0 * fanout must be below 2^30 rows";
+    const int64_t rows = n0 * io->fanout;
+    if (io->ld0 < n0 || io->ld0 >= lim) return "np_f16_model_ilqr_backward: ld0 must be at least n0 and below 2^30";
+    if (io->ld < rows || io->ld >= lim) return "np_f16_model_ilqr_backward: ld must be at least n0 * fanout and below 2^30";
+    if (io->ld_out < rows || io->ld_out >= lim) return "np_f16_model_ilqr_backward: ld_out must be at least n0 * fanout and below 2^30";
+    if (io->act_row_stride < 4 || io->act_row_stride >= lim || rows * io->act_row_stride >= lim)
+        return "np_f16_model_ilqr_backward: act_row_stride must be at least 4 floats, and n0 * fanout * act_row_stride below 2^30";
+    if (io->horizon > 1 && io->act_step_stride < (rows - 1) * io->act_row_stride + 4)
+        return "np_f16_model_ilqr_backward: act_step_stride must cover the n0 * fanout action rows of a step (a held action has no sweep)";
+    if (io->traj_step_stride < 11 * io->ld + rows) return "np_f16_model_ilqr_backward: traj_step_stride must cover one recorded state ([12][ld])";
+    if (io->max_groups < 0) return "np_f16_model_ilqr_backward: max_groups must not be negative";
+    if (!(io->mu - io->mu == 0.0f)) return "np_f16_model_ilqr_backward: mu must be finite";
+    for (int k = 0; k < 4; k++)
+        if (!(io->h_a[k] - io->h_a[k] == 0.0f) || !(io->h_a[k] + io->mu > 0.0f)) return "np_f16_model_ilqr_backward: h_a[k] + mu must be positive and finite";
+    for (int64_t k = 0; k < (int64_t)io->horizon * 12; k++)
+        if (!(io->h_s[k] - io->h_s[k] == 0.0f) || io->h_s[k] < 0.0f) return "np_f16_model_ilqr_backward: h_s must be finite and not negative";
+    return nullptr;
+}
+
+// Contexts the Riccati sweep is not built for: null, or the refusal, by name
+inline const char *ilqr_context_error(bool combat, bool fleet, bool gemm_order, bool tables, int32_t solver) {
+    if (combat) return "np_f16_model_ilqr_backward: a SingleCombat context has no model kernels (create the context with np_f16_ctx_create)";
+    if (fleet) return "np_f16_model_ilqr_backward: a context with a fleet has no Riccati sweep (it reads one airframe per context)";
+    if (gemm_order) return "np_f16_model_ilqr_backward: a context with aero_gemm_order has no Riccati sweep (built for the default order of the aero nets)";
+    if (tables) return "np_f16_model_ilqr_backward: a context with aero_1d_tables has no Riccati sweep (built for the MLP numerics)";
+    if (solver != 0) return "np_f16_model_ilqr_backward: solver: rk4 has no Riccati sweep (built for the Euler step)";
+    return nullptr;
+}
+
 }  // namespace npf16

@@ -32,6 +32,7 @@
 #include "np_model_rollout.h"
 #include "np_model_linearize.h"
 #include "np_model_rollout_vjp.h"
+#include "np_model_ilqr.h"
 namespace npact8 {
 hipError_t launch_actor_i8(const float *weights, long long n, const float *obs, const float *h_in, const float *masks, float *actions, float *h_out,
                            hipStream_t stream);   // np_actor_i8.hip
@@ -1584,6 +1585,35 @@ int np_f16_model_rollout_vjp(np_f16_ctx *ctx, int64_t n0, const np_f16_rollout_v
     a.kblob = ctx->wt.kblob;
     a.af = ctx->cfg.af;
     NP_HIP(launch_model_rollout_vjp(groups, a, (hipStream_t)stream));
+    return 0;
+}
+
+// iLQR's backward pass in one launch (np_model_ilqr.hip).  As its siblings: the record first, then the context; nothing is touched, and no
+// device call is made, before every refusal has had its turn.  h_s reaches the device through the caller's h_ws, on the launch stream.
+int np_f16_model_ilqr_backward(np_f16_ctx *ctx, int64_t n0, const np_f16_ilqr_io *io, void *stream) {
+    if (const char *e = ilqr_io_error(n0, io)) return fail(e);
+    if (!ctx) return fail("np_f16_model_ilqr_backward: null ctx");
+    if (const char *e = ilqr_context_error(ctx->combat, ctx->fleet_k > 0, ctx->gemm_order, !ctx->combat && ctx->cfg.aero_1d_tables != 0, ctx->solver)) return fail(e);
+    const int64_t rows = n0 * io->fanout;
+    int32_t groups = 0;
+    if (const char *e = linearize_groups(rows, ctx->num_cus, io->max_groups, &groups)) return fail(e);
+    DeviceGuard guard;
+    NP_HIP(guard.enter(ctx->device));
+    NP_HIP(hipMemcpyAsync(io->h_ws, io->h_s, sizeof(float) * 12 * (size_t)io->horizon, hipMemcpyHostToDevice, (hipStream_t)stream));
+    IlqrArgs a;
+    a.s0 = io->s0; a.u0 = io->u0; a.ld0 = io->ld0;
+    a.actions = io->actions; a.act_step_stride = io->act_step_stride; a.act_row_stride = io->act_row_stride;
+    a.s_traj = io->s_traj; a.g_s_traj = io->g_s_traj; a.traj_step_stride = io->traj_step_stride;
+    a.g_actions_in = io->g_actions_in; a.g_u_end = io->g_u_end; a.h_s = io->h_ws; a.mu_rows = io->mu_rows;
+    a.k = io->k; a.K = io->K; a.dV = io->dV; a.status = io->status; a.p0 = io->p0; a.P0 = io->P0;
+    a.u_ws = io->u_ws; a.p_ws = io->p_ws;
+    a.ld_traj = io->ld; a.ld_out = io->ld_out;
+    a.rows = rows;
+    a.horizon = io->horizon; a.fanout = io->fanout; a.dt = ctx->cfg.dt; a.mu = io->mu;
+    for (int k = 0; k < 4; k++) a.h_a[k] = io->h_a[k];
+    a.kblob = ctx->wt.kblob;
+    a.af = ctx->cfg.af;
+    NP_HIP(launch_model_ilqr_backward(groups, a, (hipStream_t)stream));
     return 0;
 }
 

@@ -89,6 +89,19 @@ class F16Model(BaseModel):
         s_traj, u_end = self._b.rollout_diff(actions, s, u, fanout=fanout, horizon=horizon)
         return s_traj.transpose(1, 2), u_end.t()
 
+    def ilqr_backward(self, actions, s_traj, g_s_traj, g_actions, h_s, h_a, mu, g_u_end=None, s=None, u=None, fanout=1, want_value=False):
+        """iLQR's backward pass about rollout(actions, record_every=1) as ONE kernel launch (F16Batch.ilqr_backward,
+        np_f16_model_ilqr_backward; Euler only), in this class's row-major layout: s_traj / g_s_traj [H, n * fanout, 12], g_actions
+        [H, n * fanout, 4], g_u_end [n * fanout, 4], s [n0, 12], u [n0, 5]; h_s [H, 12], h_a [4] and mu as there.
+        Returns (k [H, n * fanout, 4], K [H, n * fanout, 4, 16], dV [n * fanout, 2], status [n * fanout][, p0 [n * fanout, 16],
+        P0 [n * fanout, 16, 16]]) — strided views of the planar buffers."""
+        t = lambda x: None if x is None else torch.as_tensor(x, device=self._b.device).transpose(-1, -2)  # noqa: E731
+        out = self._b.ilqr_backward(actions, t(s_traj), t(g_s_traj), t(g_actions), h_s, h_a, mu, g_u_end=t(g_u_end), s=t(s), u=t(u), fanout=fanout,
+                                    want_value=want_value)
+        k, K, dV, status = out[:4]
+        res = (k.transpose(1, 2), K.permute(0, 3, 1, 2), dV.t(), status)
+        return res + ((out[4].t(), out[5].permute(2, 0, 1)) if want_value else ())
+
     def linearize(self, s=None, u=None, want_xdot=True):
         """xdot = f(s, u), A = df/ds, B = df/du of the flight dynamics about a flight condition, per aircraft, as ONE kernel launch
         (F16Batch.linearize, np_f16_model_linearize): what trim solvers, LQR / gain scheduling, iLQR and stability analysis start from.
