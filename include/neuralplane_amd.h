@@ -653,6 +653,60 @@ NP_STATIC_ASSERT(offsetof(np_f16_ilqr_io, mu) == 128 && offsetof(np_f16_ilqr_io,
 NP_STATIC_ASSERT(offsetof(np_f16_ilqr_io, status) == 168 && offsetof(np_f16_ilqr_io, ld_out) == 192 && offsetof(np_f16_ilqr_io, h_ws) == 216, "np_f16_ilqr_io layout");
 int np_f16_model_ilqr_backward(np_f16_ctx *ctx, int64_t n0, const np_f16_ilqr_io *io, void *stream);
 
+/* iLQR's forward pass on the flight model (a new symbol and record within ABI 16; no earlier record changes): `horizon` Euler applications of
+ * F16Model.update (envs/models/F16_model.py:51-67) under the time-varying affine feedback law np_f16_model_ilqr_backward returns, for
+ * n_alpha step sizes per problem (the line search), in ONE launch.  A pure function: nothing of the context is written.
+ *   problems and rows: laid out as np_f16_ilqr_io lays out its rows — n0 start rows, P = n0 * fanout problems, problem q starts from start
+ *         row q / fanout.  Each problem flies L = n_alpha candidates: output row r is problem q = r / L with step size alphas[r % L].
+ *         alphas is HOST memory, 1 <= L <= 64, every entry finite and in [0, 1].
+ *   per-problem inputs, in the layouts np_f16_ilqr_io consumes and produces (pitch ld): actions abar [horizon][P][>= 4] with its row and
+ *         step strides; s_traj sbar [horizon][12][ld] with traj_step_stride; k [horizon][4][ld]; K [horizon][64][ld], plane 16 a + j = K_t[a][j].
+ *   coordinates: x_t = (s_t[12], u_t[0:4]) with u_t the lagged controls ENTERING step t, as np_f16_ilqr_io's (its S = diag(1 x 12, kappa x 4)
+ *         is already in K).  sbar_0 is the start row, sbar_t = s_traj[t - 1] for t > 0; ubar_t is not an input: the kernel carries it beside u,
+ *         running the control lag on the clamped abar_t from u0 — the nominal rollout's own bits.
+ *   s_init [12][ld], u_init [5][ld] (per problem, both or neither): the state the candidates actually start from; NULL = the nominal start.
+ *         With them x_0 != xbar_0: an MPC replays its gains from the measured state.  ubar_0 always comes from u0.
+ *   the law, in this order (both kernel shapes compute the same bits):
+ *         c = fma(alpha, k_t[a], abar_t[a]);  d_j = x_t[j] - xbar_t[j];  lo = sum_{j = 0..7} K_t[a][j] d_j and hi = sum_{j = 8..15} K_t[a][j] d_j,
+ *         each a product followed by FMAs with j ascending;  a_t[a] = c + (lo + hi);  then update: clamp to [-1, 1], control lag, one Euler step.
+ *   outputs: actions_out [horizon][P L][4] row-major, the CLAMPED action of every step — what the model flew; the clamp is idempotent and
+ *         np_f16_ilqr_io's D passes gradient on [-1, 1], ends included, so np_f16_model_rollout of actions_out (record_every = 1) from the same
+ *         start reproduces s_traj_out bit for bit.  s_out [12][ld_out], u_out [5][ld_out] (row 4, lef, handed through), s_traj_out
+ *         [horizon][12][ld_out] (always recorded: the next backward pass needs it).
+ *   cost and best (optional; best needs cost, and cost needs h_s, s_ref and ws):
+ *         cost[r] = sum_t ( 1/2 sum_k h_a[k] a_t[k]^2 + 1/2 sum_k h_s[t][k] (s_{t+1}[k] - s_ref[t][k])^2 ),  a_t the clamped action,
+ *         added with t ascending and, within a step, the action's terms and then the state's, k ascending.  h_s is HOST [horizon][12], checked
+ *         finite and not negative and copied to ws on the stream; s_ref [horizon][12][ld] per problem.  This is the diagonal Gauss-Newton
+ *         model np_f16_ilqr_io takes its Hessians from; a terminal control cost and wrapped angles are the caller's business.
+ *         best[q] (int32, [P]): the candidate with the lowest finite cost, ties to the lowest index, -1 if none is finite.  Needs n_alpha a
+ *         power of two (a problem's candidates are adjacent lanes of one wave; the reduction runs in registers).
+ *   ws: workspace of 64 + 12 * horizon floats (always needed: the step sizes reach the device through it).
+ *   shape: as np_f16_rollout_io's, resolved by np_f16_rollout_shape on P * L rows.
+ *   A row whose alpha, beta or el becomes non-finite, or whose feedback has a NaN, flies NaN from there on; its cost is NaN and never wins
+ *         best; its neighbours are untouched.
+ * Everything is checked on the host before the launch (np_last_error names the field).  Refused by name: an rk4 context, a context with a
+ * fleet, with aero_gemm_order, with aero_1d_tables, and a SingleCombat context. */
+typedef struct np_f16_feedback_io {
+    const float *s0, *u0; int64_t ld0;          /* nominal start state [12][ld0], controls [5][ld0]; n0 rows */
+    const float *actions; int64_t act_step_stride, act_row_stride;   /* abar; floats */
+    int32_t horizon, fanout, n_alpha, shape;    /* shape: 0 auto, 1 throughput, 2 split */
+    const float *s_traj; int64_t traj_step_stride, ld;               /* the nominal trajectory; ld the pitch of every per-problem array */
+    const float *k, *K;                         /* [horizon][4][ld], [horizon][64][ld] */
+    const float *alphas;                        /* HOST [n_alpha] */
+    const float *s_init, *u_init;               /* [12][ld], [5][ld], or both NULL */
+    float *actions_out, *s_out, *u_out, *s_traj_out; int64_t ld_out;  /* [horizon][P L][4], [12][ld_out], [5][ld_out], [horizon][12][ld_out] */
+    float *cost; int32_t *best;                 /* [P L] or NULL; [P] or NULL */
+    const float *h_s, *s_ref;                   /* HOST [horizon][12]; [horizon][12][ld] */
+    float h_a[4];
+    float *ws;                                  /* 64 + 12 * horizon floats */
+} np_f16_feedback_io;
+NP_STATIC_ASSERT(sizeof(np_f16_feedback_io) == 224, "np_f16_feedback_io is 224 bytes");
+NP_STATIC_ASSERT(offsetof(np_f16_feedback_io, actions) == 24 && offsetof(np_f16_feedback_io, horizon) == 48 && offsetof(np_f16_feedback_io, s_traj) == 64, "np_f16_feedback_io layout");
+NP_STATIC_ASSERT(offsetof(np_f16_feedback_io, ld) == 80 && offsetof(np_f16_feedback_io, k) == 88 && offsetof(np_f16_feedback_io, alphas) == 104, "np_f16_feedback_io layout");
+NP_STATIC_ASSERT(offsetof(np_f16_feedback_io, s_init) == 112 && offsetof(np_f16_feedback_io, actions_out) == 128 && offsetof(np_f16_feedback_io, ld_out) == 160, "np_f16_feedback_io layout");
+NP_STATIC_ASSERT(offsetof(np_f16_feedback_io, cost) == 168 && offsetof(np_f16_feedback_io, h_s) == 184 && offsetof(np_f16_feedback_io, h_a) == 200 && offsetof(np_f16_feedback_io, ws) == 216, "np_f16_feedback_io layout");
+int np_f16_model_rollout_feedback(np_f16_ctx *ctx, int64_t n0, const np_f16_feedback_io *io, void *stream);
+
 /* Average duration in ms of the `count` most recent np_f16_step / np_f16_combat_step launches on this context, measured with
  * HIP events on the launch stream: a start / stop pair attached to each kernel's own dispatch (hipExtLaunchKernelGGL — the
  * timestamps of the kernel's packet, no extra barrier packets between back-to-back launches; 0 disables, enable with

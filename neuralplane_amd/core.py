@@ -654,6 +654,78 @@ class F16Batch:
         out = (k[..., :ld], K.view(h, 4, 16, lo)[..., :ld], dV[:, :ld], status)
         return out + ((p0[:, :ld], P0.view(16, 16, lo)[..., :ld]) if want_value else ())
 
+    def ilqr_forward(self, actions, s_traj, k, K, alphas, s=None, u=None, fanout=1, s_init=None, u_init=None, cost=None, shape='auto', ld_out=None, want_best=True):
+        """iLQR's forward pass as ONE launch (np_f16_model_rollout_feedback; Euler only): H update() steps under the law ilqr_backward returns,
+        a_t = abar_t + alpha k_t + K_t (x_t - xbar_t) with x = (s[12], u[0:4] entering the step), for every step size of `alphas` (host
+        values in [0, 1], at most 64) — the whole line search.  actions [H, P, >=4], s_traj [H, 12, P], k [H, 4, P] and K [H, 4, 16, P] (or
+        [H, 64, P]) are the nominal rollout and ilqr_backward's outputs for P = n0 * fanout problems; s [12, n0], u [5, n0] the nominal start
+        (omitted = the batch's current state).  s_init [12, P], u_init [5, P] (both or neither): the state the candidates actually start
+        from (an MPC replaying its gains from the measured state).  Output row r is problem r // L with step size alphas[r % L], L = len(alphas).
+        cost = (h_s [H, 12], h_a [4], s_ref [H, 12, P]): also returns the fused diagonal cost per row and the best candidate per problem
+        (the lowest finite cost, -1 if none; L a power of two — want_best=False returns the cost alone, for any L).
+        Returns (actions_new [H, P * L, 4] — the clamped actions flown: rollout(actions_new, record_every=1) is s_traj_new to the bit —,
+        s_end [12, P * L], u_end [5, P * L], s_traj_new [H, 12, P * L][, cost [P * L][, best [P] int32]]).  A pure function, as rollout;
+        the planar outputs are sliced out of [.., ld_out] allocations when ld_out > P * L."""
+        if (s is None) != (u is None):
+            raise ValueError('ilqr_forward: s and u come together (or neither: the start is the batch\'s current state)')
+        if s is None:
+            s, u = self.s, self.u
+        if s.dim() != 2 or u.dim() != 2 or s.shape[0] != 12 or u.shape[0] != 5 or s.shape[1] != u.shape[1] or s.shape[1] < 1:
+            raise ValueError(f'ilqr_forward: s must be [12, n0] and u [5, n0], got {tuple(s.shape)} and {tuple(u.shape)}')
+        f32 = dict(device=self.device, dtype=torch.float32)
+        s, u = s.to(**f32).contiguous(), u.to(**f32).contiguous()
+        n0, fanout = int(s.shape[1]), int(fanout)
+        probs = n0 * max(fanout, 0)
+        actions = torch.as_tensor(actions).to(**f32).contiguous()
+        if actions.dim() != 3 or (fanout >= 1 and (actions.shape[1] != probs or actions.shape[2] < 4)):
+            raise ValueError(f'ilqr_forward: actions must be [H, n0 * fanout = {probs}, >=4], got {tuple(actions.shape)}')
+        h, ld = int(actions.shape[0]), max(probs, 1)
+        K = torch.as_tensor(K)
+        if tuple(K.shape) == (h, 4, 16, ld):
+            K = K.reshape(h, 64, ld)
+        planar = [('s_traj', s_traj, (h, 12, ld)), ('k', k, (h, 4, ld)), ('K', K, (h, 64, ld))]
+        if (s_init is None) != (u_init is None):
+            raise ValueError('ilqr_forward: s_init and u_init come together (or neither: the candidates fly from the nominal start)')
+        planar += [('s_init', s_init, (12, ld)), ('u_init', u_init, (5, ld))] if s_init is not None else []
+        if cost is not None:
+            h_s, h_a, s_ref = cost
+            planar.append(('s_ref', s_ref, (h, 12, ld)))
+            h_s = torch.as_tensor(h_s).to(device='cpu', dtype=torch.float32).contiguous()
+            h_a = [float(x) for x in torch.as_tensor(h_a).reshape(-1).tolist()]
+            if tuple(h_s.shape) != (h, 12) or len(h_a) != 4:
+                raise ValueError(f'ilqr_forward: h_s must be [H, 12] = {(h, 12)} and h_a [4], got {tuple(h_s.shape)} and {len(h_a)} values')
+        dev = {}
+        for name, x, want in planar:
+            if tuple(x.shape) != want:
+                raise ValueError(f'ilqr_forward: {name} must be {want}, got {tuple(x.shape)}')
+            dev[name] = x.to(**f32).contiguous()
+        alphas = torch.as_tensor(alphas, dtype=torch.float32, device='cpu').reshape(-1).contiguous()
+        n_alpha = int(alphas.numel())
+        rows = ld * max(n_alpha, 1)
+        ld_out = rows if ld_out is None else int(ld_out)
+        lo = max(ld_out, 1)
+        io = _lib.NpF16FeedbackIo()
+        io.s0, io.u0, io.ld0 = s.data_ptr(), u.data_ptr(), n0
+        io.actions, io.act_row_stride, io.act_step_stride = actions.data_ptr(), actions.stride(1), actions.stride(0) if h > 1 else 0
+        io.horizon, io.fanout, io.n_alpha, io.shape = h, fanout, n_alpha, _lib.ROLLOUT_SHAPES[shape]
+        io.s_traj, io.traj_step_stride, io.ld = dev['s_traj'].data_ptr(), 12 * ld, ld
+        io.k, io.K, io.alphas = dev['k'].data_ptr(), dev['K'].data_ptr(), (alphas.data_ptr() if n_alpha else None)
+        if s_init is not None:
+            io.s_init, io.u_init = dev['s_init'].data_ptr(), dev['u_init'].data_ptr()
+        actions_new = torch.empty((h, rows, 4), **f32)
+        s_end, u_end, s_traj_new = torch.empty((12, lo), **f32), torch.empty((5, lo), **f32), torch.empty((h, 12, lo), **f32)
+        ws = torch.empty(64 + 12 * h, **f32)
+        io.actions_out, io.s_out, io.u_out, io.s_traj_out, io.ld_out = actions_new.data_ptr(), s_end.data_ptr(), u_end.data_ptr(), s_traj_new.data_ptr(), ld_out
+        io.ws = ws.data_ptr()
+        out = (actions_new, s_end[:, :rows], u_end[:, :rows], s_traj_new[..., :rows])
+        if cost is not None:
+            cost_out, best = torch.empty(rows, **f32), (torch.empty(ld, dtype=torch.int32, device=self.device) if want_best else None)
+            io.cost, io.h_s, io.s_ref, io.h_a = cost_out.data_ptr(), h_s.data_ptr(), dev['s_ref'].data_ptr(), (C.c_float * 4)(*h_a)
+            io.best = best.data_ptr() if want_best else None
+            out += (cost_out, best) if want_best else (cost_out,)
+        _lib.check(self.lib.np_f16_model_rollout_feedback(self._ctx, n0, C.byref(io), self._stream()))
+        return out
+
     def rollout_diff(self, actions, s=None, u=None, fanout=1, horizon=None):
         """rollout(record_every=1) that loss.backward() works through: returns (s_traj [H, 12, n0 * fanout], u_end [5, n0 * fanout]), the
         forward pass the very rollout launch (bit-identical), the backward pass ONE rollout_vjp launch.  Differentiable with respect to

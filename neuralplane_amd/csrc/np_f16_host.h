@@ -601,4 +601,61 @@ inline const char *ilqr_context_error(bool combat, bool fleet, bool gemm_order, 
     return nullptr;
 }
 
+// ---- np_f16_model_rollout_feedback (np_model_rollout_fb.hip) -------------------------------------------------------------------------
+// The record of a feedback rollout over n0 start rows, checked before anything is launched: null, or the first thing wrong with it.  The
+// limits are the rollout's, for P = n0 * fanout problems and P * n_alpha output rows (below 2^28: a row of actions_out is 16 bytes behind
+// a 32-bit offset).  alphas and h_s are HOST memory and are read here.
+constexpr int32_t FEEDBACK_MAX_ALPHAS = 64;
+inline const char *feedback_io_error(int64_t n0, const np_f16_feedback_io *io) {
+    if (!io) return "np_f16_model_rollout_feedback: null io";
+    if (io->horizon < 1) return "np_f16_model_rollout_feedback: horizon must be at least 1";
+    if (io->fanout < 1) return "np_f16_model_rollout_feedback: fanout must be at least 1";
+    if (n0 < 1) return "np_f16_model_rollout_feedback: n0 must be at least 1";
+    if (io->n_alpha < 1 || io->n_alpha > FEEDBACK_MAX_ALPHAS) return "np_f16_model_rollout_feedback: n_alpha must be in [1, 64]";
+    if (!io->alphas) return "np_f16_model_rollout_feedback: null step sizes (alphas, host memory)";
+    for (int32_t k = 0; k < io->n_alpha; k++)
+        if (!(io->alphas[k] >= 0.0f && io->alphas[k] <= 1.0f)) return "np_f16_model_rollout_feedback: alphas must be finite and in [0, 1]";
+    if (!io->s0 || !io->u0) return "np_f16_model_rollout_feedback: null start state / controls (s0, u0)";
+    if (!io->actions) return "np_f16_model_rollout_feedback: null actions";
+    if (!io->s_traj) return "np_f16_model_rollout_feedback: null nominal trajectory (s_traj)";
+    if (!io->k || !io->K) return "np_f16_model_rollout_feedback: null gains (k, K)";
+    if ((io->s_init == nullptr) != (io->u_init == nullptr)) return "np_f16_model_rollout_feedback: s_init and u_init come together (or neither)";
+    if (!io->actions_out || !io->s_out || !io->u_out || !io->s_traj_out)
+        return "np_f16_model_rollout_feedback: null output (actions_out, s_out, u_out, s_traj_out)";
+    if (!io->ws) return "np_f16_model_rollout_feedback: null workspace (ws)";
+    if (io->best && !io->cost) return "np_f16_model_rollout_feedback: best needs cost";
+    if (io->cost && (!io->h_s || !io->s_ref)) return "np_f16_model_rollout_feedback: cost needs h_s (host memory) and s_ref";
+    if (io->best && (io->n_alpha & (io->n_alpha - 1)) != 0)
+        return "np_f16_model_rollout_feedback: best needs n_alpha to be a power of two (a problem's candidates are the lanes of one aligned group)";
+    const int64_t lim = 1ll << 30, lim_rows = 1ll << 28;
+    if (n0 >= lim || io->fanout >= lim || n0 * io->fanout >= lim) return "np_f16_model_rollout_feedback: n0 * fanout must be below 2^30 problems";
+    const int64_t probs = n0 * io->fanout, rows = probs * io->n_alpha;
+    if (rows >= lim_rows) return "np_f16_model_rollout_feedback: n0 * fanout * n_alpha must be below 2^28 rows";
+    if (io->ld0 < n0 || io->ld0 >= lim) return "np_f16_model_rollout_feedback: ld0 must be at least n0 and below 2^30";
+    if (io->ld < probs || io->ld >= lim) return "np_f16_model_rollout_feedback: ld must be at least n0 * fanout and below 2^30";
+    if (io->ld_out < rows || io->ld_out >= lim) return "np_f16_model_rollout_feedback: ld_out must be at least n0 * fanout * n_alpha and below 2^30";
+    if (io->act_row_stride < 4 || io->act_row_stride >= lim || probs * io->act_row_stride >= lim)
+        return "np_f16_model_rollout_feedback: act_row_stride must be at least 4 floats, and n0 * fanout * act_row_stride below 2^30";
+    if (io->horizon > 1 && io->act_step_stride < (probs - 1) * io->act_row_stride + 4)
+        return "np_f16_model_rollout_feedback: act_step_stride must cover the n0 * fanout action rows of a step";
+    if (io->traj_step_stride < 11 * io->ld + probs) return "np_f16_model_rollout_feedback: traj_step_stride must cover one recorded state ([12][ld])";
+    if (io->cost) {
+        for (int k = 0; k < 4; k++)
+            if (!(io->h_a[k] - io->h_a[k] == 0.0f) || io->h_a[k] < 0.0f) return "np_f16_model_rollout_feedback: h_a must be finite and not negative";
+        for (int64_t k = 0; k < (int64_t)io->horizon * 12; k++)
+            if (!(io->h_s[k] - io->h_s[k] == 0.0f) || io->h_s[k] < 0.0f) return "np_f16_model_rollout_feedback: h_s must be finite and not negative";
+    }
+    return nullptr;
+}
+
+// Contexts the feedback rollout is not built for: null, or the refusal, by name (those of the reverse sweep)
+inline const char *feedback_context_error(bool combat, bool fleet, bool gemm_order, bool tables, int32_t solver) {
+    if (combat) return "np_f16_model_rollout_feedback: a SingleCombat context has no model kernels (create the context with np_f16_ctx_create)";
+    if (fleet) return "np_f16_model_rollout_feedback: a context with a fleet has no feedback rollout (it reads one airframe per context)";
+    if (gemm_order) return "np_f16_model_rollout_feedback: a context with aero_gemm_order has no feedback rollout (built for the default order of the aero nets)";
+    if (tables) return "np_f16_model_rollout_feedback: a context with aero_1d_tables has no feedback rollout (built for the MLP numerics)";
+    if (solver != 0) return "np_f16_model_rollout_feedback: solver: rk4 has no feedback rollout (built for the Euler step)";
+    return nullptr;
+}
+
 }  // namespace npf16

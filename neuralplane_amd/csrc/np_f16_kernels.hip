@@ -33,6 +33,7 @@
 #include "np_model_linearize.h"
 #include "np_model_rollout_vjp.h"
 #include "np_model_ilqr.h"
+#include "np_model_rollout_fb.h"
 namespace npact8 {
 hipError_t launch_actor_i8(const float *weights, long long n, const float *obs, const float *h_in, const float *masks, float *actions, float *h_out,
                            hipStream_t stream);   // np_actor_i8.hip
@@ -1614,6 +1615,40 @@ int np_f16_model_ilqr_backward(np_f16_ctx *ctx, int64_t n0, const np_f16_ilqr_io
     a.kblob = ctx->wt.kblob;
     a.af = ctx->cfg.af;
     NP_HIP(launch_model_ilqr_backward(groups, a, (hipStream_t)stream));
+    return 0;
+}
+
+// iLQR's forward pass in one launch (np_model_rollout_fb.hip).  As its siblings: the record first, then the context; nothing is touched, and
+// no device call is made, before every refusal has had its turn.  The step sizes and h_s reach the device through the caller's ws, on the
+// launch stream.
+static_assert(FEEDBACK_MAX_ALPHAS == FB_WS_ALPHAS, "np_f16_host.h mirrors np_model_rollout_fb.h");
+int np_f16_model_rollout_feedback(np_f16_ctx *ctx, int64_t n0, const np_f16_feedback_io *io, void *stream) {
+    if (const char *e = feedback_io_error(n0, io)) return fail(e);
+    if (!ctx) return fail("np_f16_model_rollout_feedback: null ctx");
+    if (const char *e = feedback_context_error(ctx->combat, ctx->fleet_k > 0, ctx->gemm_order, !ctx->combat && ctx->cfg.aero_1d_tables != 0, ctx->solver)) return fail(e);
+    const int64_t rows = n0 * io->fanout * io->n_alpha;
+    int32_t shape = 0;
+    if (const char *e = rollout_shape(rows, ctx->num_cus, ctx->solver, io->shape, &shape)) return fail(e);
+    DeviceGuard guard;
+    NP_HIP(guard.enter(ctx->device));
+    NP_HIP(hipMemcpyAsync(io->ws, io->alphas, sizeof(float) * (size_t)io->n_alpha, hipMemcpyHostToDevice, (hipStream_t)stream));
+    if (io->cost)
+        NP_HIP(hipMemcpyAsync(io->ws + FB_WS_ALPHAS, io->h_s, sizeof(float) * 12 * (size_t)io->horizon, hipMemcpyHostToDevice, (hipStream_t)stream));
+    FeedbackArgs a;
+    a.s0 = io->s0; a.u0 = io->u0; a.ld0 = io->ld0;
+    a.actions = io->actions; a.act_step_stride = io->horizon > 1 ? io->act_step_stride : 0; a.act_row_stride = io->act_row_stride;
+    a.s_traj = io->s_traj; a.traj_step_stride = io->traj_step_stride;
+    a.k = io->k; a.K = io->K; a.s_init = io->s_init; a.u_init = io->u_init;
+    a.s_ref = io->cost ? io->s_ref : nullptr; a.ws = io->ws;
+    a.actions_out = io->actions_out; a.s_out = io->s_out; a.u_out = io->u_out; a.s_traj_out = io->s_traj_out;
+    a.cost = io->cost; a.best = io->best;
+    a.ld = io->ld; a.ld_out = io->ld_out;
+    a.rows = rows;
+    a.horizon = io->horizon; a.fanout = io->fanout; a.n_alpha = io->n_alpha; a.pad_ = 0;
+    for (int k = 0; k < 4; k++) a.h_a[k] = io->cost ? io->h_a[k] : 0.0f;
+    a.cfg.dt = ctx->cfg.dt; a.cfg.pad_ = 0; a.cfg.af = ctx->cfg.af;
+    a.wt = ctx->wt;
+    NP_HIP(launch_model_rollout_feedback(shape, a, (hipStream_t)stream));
     return 0;
 }
 

@@ -102,6 +102,19 @@ class F16Model(BaseModel):
         res = (k.transpose(1, 2), K.permute(0, 3, 1, 2), dV.t(), status)
         return res + ((out[4].t(), out[5].permute(2, 0, 1)) if want_value else ())
 
+    def ilqr_forward(self, actions, s_traj, k, K, alphas, s=None, u=None, fanout=1, s_init=None, u_init=None, cost=None, shape='auto', want_best=True):
+        """iLQR's forward pass — the feedback rollout under ilqr_backward's gains for every step size of `alphas` — as ONE kernel launch
+        (F16Batch.ilqr_forward, np_f16_model_rollout_feedback; Euler only), in this class's row-major layout: s_traj [H, P, 12], k [H, P, 4],
+        K [H, P, 4, 16], s [n0, 12], u [n0, 5], s_init [P, 12], u_init [P, 5], cost = (h_s [H, 12], h_a [4], s_ref [H, P, 12]).
+        Returns (actions_new [H, P * L, 4], s_end [P * L, 12], u_end [P * L, 5], s_traj_new [H, P * L, 12][, cost [P * L][, best [P]]]) —
+        strided views of the planar buffers; row r is problem r // L with step size alphas[r % L]."""
+        t = lambda x: None if x is None else torch.as_tensor(x, device=self._b.device).transpose(-1, -2)  # noqa: E731
+        if cost is not None:
+            cost = (cost[0], cost[1], t(cost[2]))
+        out = self._b.ilqr_forward(actions, t(s_traj), t(k), torch.as_tensor(K, device=self._b.device).permute(0, 2, 3, 1), alphas, s=t(s), u=t(u),
+                                   fanout=fanout, s_init=t(s_init), u_init=t(u_init), cost=cost, shape=shape, want_best=want_best)
+        return (out[0], out[1].t(), out[2].t(), out[3].transpose(1, 2)) + out[4:]
+
     def linearize(self, s=None, u=None, want_xdot=True):
         """xdot = f(s, u), A = df/ds, B = df/du of the flight dynamics about a flight condition, per aircraft, as ONE kernel launch
         (F16Batch.linearize, np_f16_model_linearize): what trim solvers, LQR / gain scheduling, iLQR and stability analysis start from.
