@@ -707,6 +707,56 @@ NP_STATIC_ASSERT(offsetof(np_f16_feedback_io, s_init) == 112 && offsetof(np_f16_
 NP_STATIC_ASSERT(offsetof(np_f16_feedback_io, cost) == 168 && offsetof(np_f16_feedback_io, h_s) == 184 && offsetof(np_f16_feedback_io, h_a) == 200 && offsetof(np_f16_feedback_io, ws) == 216, "np_f16_feedback_io layout");
 int np_f16_model_rollout_feedback(np_f16_ctx *ctx, int64_t n0, const np_f16_feedback_io *io, void *stream);
 
+/* One MPPI iteration on the flight model (a new symbol and record within ABI 16; no earlier record changes): for each of P = n0 problems,
+ * K = `candidates` action sequences are sampled around the problem's plan, flown for `horizon` Euler applications of F16Model.update
+ * (envs/models/F16_model.py:51-67), costed, and folded into one new plan by softmin weights — two kernels enqueued back to back by this
+ * ONE call; no noise, candidate or trajectory array is ever in memory.  A pure function: nothing of the context is written.
+ *   problems and rows: problem q starts from start row q (s0 [12][ld0], u0 [5][ld0]; row 4, lef, is not read).  Row r of the P K rows is
+ *         problem q = r / K, candidate c = r % K.  1 <= K <= 4096, any integer; P K below 2^28.
+ *   noise: eps[r][t][0:4] is the first four normals of the numerics spec's draw for (seed, call_idx = call0 + t / hold,
+ *         row = r): pairs 0 and 1 of Philox counter block 2, statement for statement what the observation noise adds to o[0..3] at scale 1.
+ *         hold >= 1 keeps a draw for `hold` steps.  Candidate 0 of every problem flies eps = 0: the nominal plan is always a candidate.
+ *         The caller advances call0 by at least ceil(horizon / hold) between calls.
+ *   candidates: a[r][t][k] = clamp(fma(sigma[k], eps[r][t][k], abar[q][t][k]), -1, 1), NaN staying NaN; then update runs exactly as
+ *         np_f16_model_rollout runs it.  abar = actions [horizon][P][>= 4] with its row and step strides; sigma[4] finite and >= 0.
+ *   cost: np_f16_feedback_io's, unchanged:
+ *         cost[r] = sum_t ( 1/2 sum_k h_a[k] a_t[k]^2 + 1/2 sum_k h_s[t][k] (s_{t+1}[k] - s_ref[t][k])^2 ),  a_t the clamped action,
+ *         added with t ascending and, within a step, the action's terms and then the state's, k ascending.  h_s is HOST [horizon][12] and
+ *         h_a[4], both finite and not negative; h_s is copied to ws on the stream; s_ref [horizon][12][ld] per problem.  cost [P K] is
+ *         always written (the second kernel reads it).
+ *   update: over a problem's finite costs cmin is the lowest; w_c = exp(-(cost_c - cmin) / temperature) (0 for a non-finite cost), divided
+ *         by their sum;  plan_out[t][q][k] = sum_c w_c a[q K + c][t][k], [horizon][P][4] row-major, 16-byte aligned: a convex combination of
+ *         actions flown, so it stays in [-1, 1].  temperature finite and > 0.
+ *   best [P] (int32, optional): the candidate with the lowest finite cost, ties to the lowest index, -1 if none is finite.
+ *   ess [P] (optional): 1 / sum_c w_c^2, or 0 if no candidate is finite.  If none is finite, plan_out is the clamped nominal.
+ *   actions_out [horizon][P K][4] (optional, 16-byte aligned): the candidates flown; np_f16_model_rollout of it with fanout = K is the
+ *         flight that was costed.  When it is NULL no per-step store happens at all.
+ *   ws: workspace of 12 * horizon floats.   shape: as np_f16_rollout_io's, resolved by np_f16_rollout_shape on P K rows; both shapes
+ *         compute the same bits.
+ *   A row whose alpha, beta or el becomes non-finite flies NaN from there on: its cost is NaN and its weight 0; its neighbours are untouched.
+ * Everything is checked on the host before the first launch (np_last_error names the field).  Refused by name: an rk4 context, a context
+ * with a fleet, with aero_gemm_order, with aero_1d_tables, and a SingleCombat context. */
+typedef struct np_f16_mppi_io {
+    const float *s0, *u0; int64_t ld0;          /* start state [12][ld0], controls [5][ld0]; n0 = P rows */
+    const float *actions; int64_t act_step_stride, act_row_stride;   /* abar; floats */
+    int32_t horizon, candidates, hold, shape;   /* shape: 0 auto, 1 throughput, 2 split */
+    uint64_t seed, call0;
+    float sigma[4];
+    float temperature; int32_t reserved_;       /* reserved_ must be 0 */
+    const float *h_s, *s_ref; int64_t ld;       /* HOST [horizon][12]; [horizon][12][ld] */
+    float h_a[4];
+    float *cost, *plan_out;                     /* [P K]; [horizon][P][4] */
+    int32_t *best; float *ess;                  /* [P] or NULL; [P] or NULL */
+    float *actions_out;                         /* [horizon][P K][4] or NULL */
+    float *ws;                                  /* 12 * horizon floats */
+} np_f16_mppi_io;
+NP_STATIC_ASSERT(sizeof(np_f16_mppi_io) == 192, "np_f16_mppi_io is 192 bytes");
+NP_STATIC_ASSERT(offsetof(np_f16_mppi_io, actions) == 24 && offsetof(np_f16_mppi_io, horizon) == 48 && offsetof(np_f16_mppi_io, seed) == 64, "np_f16_mppi_io layout");
+NP_STATIC_ASSERT(offsetof(np_f16_mppi_io, sigma) == 80 && offsetof(np_f16_mppi_io, temperature) == 96 && offsetof(np_f16_mppi_io, h_s) == 104, "np_f16_mppi_io layout");
+NP_STATIC_ASSERT(offsetof(np_f16_mppi_io, ld) == 120 && offsetof(np_f16_mppi_io, h_a) == 128 && offsetof(np_f16_mppi_io, cost) == 144, "np_f16_mppi_io layout");
+NP_STATIC_ASSERT(offsetof(np_f16_mppi_io, best) == 160 && offsetof(np_f16_mppi_io, actions_out) == 176 && offsetof(np_f16_mppi_io, ws) == 184, "np_f16_mppi_io layout");
+int np_f16_model_mppi(np_f16_ctx *ctx, int64_t n0, const np_f16_mppi_io *io, void *stream);
+
 /* Average duration in ms of the `count` most recent np_f16_step / np_f16_combat_step launches on this context, measured with
  * HIP events on the launch stream: a start / stop pair attached to each kernel's own dispatch (hipExtLaunchKernelGGL — the
  * timestamps of the kernel's packet, no extra barrier packets between back-to-back launches; 0 disables, enable with

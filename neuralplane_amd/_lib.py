@@ -178,6 +178,16 @@ class NpF16FeedbackIo(C.Structure):   # include/neuralplane_amd.h: np_f16_feedba
                 ('ws', C.c_void_p)]
 
 
+class NpF16MppiIo(C.Structure):   # include/neuralplane_amd.h: np_f16_mppi_io
+    _fields_ = [('s0', C.c_void_p), ('u0', C.c_void_p), ('ld0', C.c_int64),
+                ('actions', C.c_void_p), ('act_step_stride', C.c_int64), ('act_row_stride', C.c_int64),
+                ('horizon', C.c_int32), ('candidates', C.c_int32), ('hold', C.c_int32), ('shape', C.c_int32),
+                ('seed', C.c_uint64), ('call0', C.c_uint64), ('sigma', C.c_float * 4), ('temperature', C.c_float), ('reserved_', C.c_int32),
+                ('h_s', C.c_void_p), ('s_ref', C.c_void_p), ('ld', C.c_int64), ('h_a', C.c_float * 4),
+                ('cost', C.c_void_p), ('plan_out', C.c_void_p), ('best', C.c_void_p), ('ess', C.c_void_p), ('actions_out', C.c_void_p),
+                ('ws', C.c_void_p)]
+
+
 def linearize_groups(n, num_cus, max_groups=0):
     """np_f16_linearize_groups: the workgroups a linearisation of n rows launches on a device with num_cus CUs.  No GPU needed."""
     lib = load()
@@ -215,7 +225,7 @@ def pack_kblob_gemm(blob):
 EXPORTS = ('np_abi_version', 'np_f16_airframe_default', 'np_f16_cache_floats', 'np_last_error', 'np_f16_ctx_create', 'np_f16_ctx_destroy', 'np_f16_reset',
            'np_f16_step', 'np_f16_derived', 'np_f16_aero_coefficients', 'np_f16_lowlevel_obs', 'np_f16_set_timing', 'np_f16_get_timing', 'np_f16_get_timing_samples', 'np_f16_set_trace', 'np_selfcheck_divc', 'np_selfcheck_math',
            'np_f16_combat_ctx_create', 'np_f16_combat_reset', 'np_f16_combat_step', 'np_f16_set_kernel_variant', 'np_actor_forward', 'np_rollout_returns', 'np_planning_inner_loop', 'np_planning_check', 'np_actor_pack_i8', 'np_rollout_insert', 'np_policy_act', 'np_planning_targets_obs', 'np_dispatch_plan', 'np_dispatch_plan_gemm', 'np_f16_pack_kblob_gemm',
-           'np_f16_set_fleet', 'np_f16_set_fleet_index', 'np_f16_model_rollout', 'np_f16_rollout_shape', 'np_f16_model_linearize', 'np_f16_linearize_groups', 'np_f16_model_rollout_vjp', 'np_f16_model_ilqr_backward', 'np_f16_model_rollout_feedback')
+           'np_f16_set_fleet', 'np_f16_set_fleet_index', 'np_f16_model_rollout', 'np_f16_rollout_shape', 'np_f16_model_linearize', 'np_f16_linearize_groups', 'np_f16_model_rollout_vjp', 'np_f16_model_ilqr_backward', 'np_f16_model_rollout_feedback', 'np_f16_model_mppi')
 KERNEL_VARIANTS = {'auto': 0, 'latency': 1, 'throughput': 2, 'pair': 3, 'latency8': 4, 'latency2': 5, 'latency4w': 6, 'dual8': 7, 'dual4': 8}
 
 _lib = None
@@ -274,6 +284,8 @@ def load():
         lib.np_f16_model_ilqr_backward.argtypes = [C.c_void_p, C.c_int64, C.POINTER(NpF16IlqrIo), C.c_void_p]
     if hasattr(lib, 'np_f16_model_rollout_feedback'):
         lib.np_f16_model_rollout_feedback.argtypes = [C.c_void_p, C.c_int64, C.POINTER(NpF16FeedbackIo), C.c_void_p]
+    if hasattr(lib, 'np_f16_model_mppi'):
+        lib.np_f16_model_mppi.argtypes = [C.c_void_p, C.c_int64, C.POINTER(NpF16MppiIo), C.c_void_p]
     lib.np_actor_forward.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_int, C.c_void_p]
     lib.np_planning_inner_loop.argtypes = [C.c_void_p, C.c_int64, C.POINTER(NpF16Io), C.POINTER(NpPlanningLoop), C.c_void_p]

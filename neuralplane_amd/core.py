@@ -186,6 +186,7 @@ class F16Batch:
         self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         self.row0 = int(row0)
         self.call_idx = 0
+        self.mppi_call = 0   # mppi()'s own draw counter: a planner's noise never moves the env's observation-noise stream
         with open(blob_path, 'rb') as f:
             blob = f.read()
         ctx = C.c_void_p()
@@ -725,6 +726,55 @@ class F16Batch:
             out += (cost_out, best) if want_best else (cost_out,)
         _lib.check(self.lib.np_f16_model_rollout_feedback(self._ctx, n0, C.byref(io), self._stream()))
         return out
+
+    def mppi(self, actions, sigma, temperature, cost, candidates, s=None, u=None, seed=None, call0=None, hold=1, shape='auto', want_candidates=False):
+        """One MPPI iteration as ONE library call of two launches (np_f16_model_mppi; Euler only): for each of the P = n0 problems, K =
+        `candidates` action sequences a = clamp(actions + sigma * eps) are flown for H update() steps from s [12, P], u [5, P] (omitted = the
+        batch's current state), costed with cost = (h_s [H, 12], h_a [4], s_ref [H, 12, P]) — ilqr_forward's fused diagonal cost — and folded
+        into the new plan by softmin weights exp(-(cost - min) / temperature).  actions [H, P, >=4] is the plan; sigma a number or four.
+        eps is the numerics spec's counter-based normal draw for (seed, call0 + t // hold, row): no noise, candidate or trajectory tensor
+        exists.  Candidate 0 of every problem is the plan itself.  seed defaults to the batch's; call0 to this batch's own mppi counter,
+        which the call then advances by ceil(H / hold) — the env's call_idx is not touched.
+        Returns (plan [H, P, 4], cost [P * K] (row r = candidate r % K of problem r // K), best [P] int32 (-1: no finite candidate, the plan is
+        then the clamped input), ess [P][, candidates [H, P * K, 4] — the actions flown]).  A pure function, as rollout."""
+        if (s is None) != (u is None):
+            raise ValueError('mppi: s and u come together (or neither: the start is the batch\'s current state)')
+        if s is None:
+            s, u = self.s, self.u
+        if s.dim() != 2 or u.dim() != 2 or s.shape[0] != 12 or u.shape[0] != 5 or s.shape[1] != u.shape[1] or s.shape[1] < 1:
+            raise ValueError(f'mppi: s must be [12, P] and u [5, P], got {tuple(s.shape)} and {tuple(u.shape)}')
+        f32 = dict(device=self.device, dtype=torch.float32)
+        s, u = s.to(**f32).contiguous(), u.to(**f32).contiguous()
+        P, K, hold = int(s.shape[1]), int(candidates), int(hold)
+        actions = torch.as_tensor(actions).to(**f32).contiguous()
+        if actions.dim() != 3 or actions.shape[1] != P or actions.shape[2] < 4:
+            raise ValueError(f'mppi: actions must be [H, P = {P}, >=4], got {tuple(actions.shape)}')
+        h = int(actions.shape[0])
+        h_s, h_a, s_ref = cost
+        h_s = torch.as_tensor(h_s).to(device='cpu', dtype=torch.float32).contiguous()
+        h_a = [float(x) for x in torch.as_tensor(h_a).reshape(-1).tolist()]
+        sigma = [float(x) for x in torch.as_tensor(sigma, dtype=torch.float32).reshape(-1).tolist()]
+        sigma = sigma * 4 if len(sigma) == 1 else sigma
+        if tuple(h_s.shape) != (h, 12) or len(h_a) != 4 or len(sigma) != 4 or tuple(s_ref.shape) != (h, 12, P):
+            raise ValueError(f'mppi: h_s must be [H, 12] = {(h, 12)}, h_a [4], sigma a number or [4] and s_ref [H, 12, P] = {(h, 12, P)}')
+        s_ref = s_ref.to(**f32).contiguous()
+        rows = P * max(K, 1)
+        io = _lib.NpF16MppiIo()
+        io.s0, io.u0, io.ld0 = s.data_ptr(), u.data_ptr(), P
+        io.actions, io.act_row_stride, io.act_step_stride = actions.data_ptr(), actions.stride(1), actions.stride(0) if h > 1 else 0
+        io.horizon, io.candidates, io.hold, io.shape = h, K, hold, _lib.ROLLOUT_SHAPES[shape]
+        io.seed, io.call0 = (self.seed if seed is None else int(seed) & 0xFFFFFFFFFFFFFFFF), (self.mppi_call if call0 is None else int(call0))
+        io.sigma, io.temperature, io.h_a = (C.c_float * 4)(*sigma), float(temperature), (C.c_float * 4)(*h_a)
+        io.h_s, io.s_ref, io.ld = h_s.data_ptr(), s_ref.data_ptr(), P
+        plan, cost_out, ess = torch.empty((h, P, 4), **f32), torch.empty(rows, **f32), torch.empty(P, **f32)
+        best, ws = torch.empty(P, dtype=torch.int32, device=self.device), torch.empty(12 * h, **f32)
+        flown = torch.empty((h, rows, 4), **f32) if want_candidates else None
+        io.cost, io.plan_out, io.best, io.ess, io.ws = cost_out.data_ptr(), plan.data_ptr(), best.data_ptr(), ess.data_ptr(), ws.data_ptr()
+        io.actions_out = flown.data_ptr() if want_candidates else None
+        _lib.check(self.lib.np_f16_model_mppi(self._ctx, P, C.byref(io), self._stream()))
+        if call0 is None:
+            self.mppi_call += -(-h // max(hold, 1))
+        return (plan, cost_out, best, ess) + ((flown,) if want_candidates else ())
 
     def rollout_diff(self, actions, s=None, u=None, fanout=1, horizon=None):
         """rollout(record_every=1) that loss.backward() works through: returns (s_traj [H, 12, n0 * fanout], u_end [5, n0 * fanout]), the

@@ -658,4 +658,52 @@ inline const char *feedback_context_error(bool combat, bool fleet, bool gemm_ord
     return nullptr;
 }
 
+// ---- np_f16_model_mppi (np_model_mppi.hip) --------------------------------------------------------------------------------------------
+// The record of an MPPI iteration over n0 = P problems, checked before anything is launched: null, or the first thing wrong with it.  The
+// row limits are the feedback rollout's, for P problems and P * candidates output rows.  sigma, h_a and h_s are HOST memory and are read here.
+constexpr int32_t MPPI_CANDIDATES_LIMIT = 4096;
+inline const char *mppi_io_error(int64_t n0, const np_f16_mppi_io *io) {
+    if (!io) return "np_f16_model_mppi: null io";
+    if (io->horizon < 1) return "np_f16_model_mppi: horizon must be at least 1";
+    if (n0 < 1) return "np_f16_model_mppi: n0 must be at least 1";
+    if (io->candidates < 1 || io->candidates > MPPI_CANDIDATES_LIMIT) return "np_f16_model_mppi: candidates (K) must be in [1, 4096]";
+    if (io->hold < 1) return "np_f16_model_mppi: hold must be at least 1";
+    if (io->reserved_ != 0) return "np_f16_model_mppi: reserved_ must be 0";
+    for (int k = 0; k < 4; k++)
+        if (!(io->sigma[k] - io->sigma[k] == 0.0f) || io->sigma[k] < 0.0f) return "np_f16_model_mppi: sigma must be finite and not negative";
+    if (!(io->temperature - io->temperature == 0.0f) || !(io->temperature > 0.0f)) return "np_f16_model_mppi: temperature must be finite and positive";
+    if (!io->s0 || !io->u0) return "np_f16_model_mppi: null start state / controls (s0, u0)";
+    if (!io->actions) return "np_f16_model_mppi: null actions";
+    if (!io->cost) return "np_f16_model_mppi: null cost (always written: the re-weighting pass reads it)";
+    if (!io->plan_out) return "np_f16_model_mppi: null output (plan_out)";
+    if (!io->h_s) return "np_f16_model_mppi: null state cost diagonal (h_s, host memory)";
+    if (!io->s_ref) return "np_f16_model_mppi: null cost reference (s_ref)";
+    if (!io->ws) return "np_f16_model_mppi: null workspace (ws)";
+    const int64_t lim = 1ll << 30, lim_rows = 1ll << 28;
+    if (n0 >= lim) return "np_f16_model_mppi: n0 must be below 2^30 problems";
+    const int64_t rows = n0 * io->candidates;
+    if (rows >= lim_rows) return "np_f16_model_mppi: n0 * candidates must be below 2^28 rows";
+    if (io->ld0 < n0 || io->ld0 >= lim) return "np_f16_model_mppi: ld0 must be at least n0 and below 2^30";
+    if (io->ld < n0 || io->ld >= lim) return "np_f16_model_mppi: ld must be at least n0 and below 2^30";
+    if (io->act_row_stride < 4 || io->act_row_stride >= lim || n0 * io->act_row_stride >= lim)
+        return "np_f16_model_mppi: act_row_stride must be at least 4 floats, and n0 * act_row_stride below 2^30";
+    if (io->horizon > 1 && io->act_step_stride < (n0 - 1) * io->act_row_stride + 4)
+        return "np_f16_model_mppi: act_step_stride must cover the n0 action rows of a step";
+    for (int k = 0; k < 4; k++)
+        if (!(io->h_a[k] - io->h_a[k] == 0.0f) || io->h_a[k] < 0.0f) return "np_f16_model_mppi: h_a must be finite and not negative";
+    for (int64_t k = 0; k < (int64_t)io->horizon * 12; k++)
+        if (!(io->h_s[k] - io->h_s[k] == 0.0f) || io->h_s[k] < 0.0f) return "np_f16_model_mppi: h_s must be finite and not negative";
+    return nullptr;
+}
+
+// Contexts the MPPI kernels are not built for: null, or the refusal, by name (those of the feedback rollout)
+inline const char *mppi_context_error(bool combat, bool fleet, bool gemm_order, bool tables, int32_t solver) {
+    if (combat) return "np_f16_model_mppi: a SingleCombat context has no model kernels (create the context with np_f16_ctx_create)";
+    if (fleet) return "np_f16_model_mppi: a context with a fleet has no MPPI step (it reads one airframe per context)";
+    if (gemm_order) return "np_f16_model_mppi: a context with aero_gemm_order has no MPPI step (built for the default order of the aero nets)";
+    if (tables) return "np_f16_model_mppi: a context with aero_1d_tables has no MPPI step (built for the MLP numerics)";
+    if (solver != 0) return "np_f16_model_mppi: solver: rk4 has no MPPI step (built for the Euler step)";
+    return nullptr;
+}
+
 }  // namespace npf16

@@ -34,6 +34,7 @@
 #include "np_model_rollout_vjp.h"
 #include "np_model_ilqr.h"
 #include "np_model_rollout_fb.h"
+#include "np_model_mppi.h"
 namespace npact8 {
 hipError_t launch_actor_i8(const float *weights, long long n, const float *obs, const float *h_in, const float *masks, float *actions, float *h_out,
                            hipStream_t stream);   // np_actor_i8.hip
@@ -1649,6 +1650,38 @@ int np_f16_model_rollout_feedback(np_f16_ctx *ctx, int64_t n0, const np_f16_feed
     a.cfg.dt = ctx->cfg.dt; a.cfg.pad_ = 0; a.cfg.af = ctx->cfg.af;
     a.wt = ctx->wt;
     NP_HIP(launch_model_rollout_feedback(shape, a, (hipStream_t)stream));
+    return 0;
+}
+
+// One MPPI iteration, two launches back to back (np_model_mppi.hip).  As its siblings: the record first, then the context; nothing is touched,
+// and no device call is made, before every refusal has had its turn.  h_s reaches the device through the caller's ws, on the launch stream.
+static_assert(MPPI_CANDIDATES_LIMIT == MPPI_MAX_CANDIDATES, "np_f16_host.h mirrors np_model_mppi.h");
+int np_f16_model_mppi(np_f16_ctx *ctx, int64_t n0, const np_f16_mppi_io *io, void *stream) {
+    if (const char *e = mppi_io_error(n0, io)) return fail(e);
+    if (!ctx) return fail("np_f16_model_mppi: null ctx");
+    if (const char *e = mppi_context_error(ctx->combat, ctx->fleet_k > 0, ctx->gemm_order, !ctx->combat && ctx->cfg.aero_1d_tables != 0, ctx->solver)) return fail(e);
+    const int64_t rows = n0 * io->candidates;
+    int32_t shape = 0;
+    if (const char *e = rollout_shape(rows, ctx->num_cus, ctx->solver, io->shape, &shape)) return fail(e);
+    DeviceGuard guard;
+    NP_HIP(guard.enter(ctx->device));
+    NP_HIP(hipMemcpyAsync(io->ws, io->h_s, sizeof(float) * 12 * (size_t)io->horizon, hipMemcpyHostToDevice, (hipStream_t)stream));
+    MppiArgs a;
+    a.s0 = io->s0; a.u0 = io->u0; a.ld0 = io->ld0;
+    a.actions = io->actions; a.act_step_stride = io->horizon > 1 ? io->act_step_stride : 0; a.act_row_stride = io->act_row_stride;
+    a.s_ref = io->s_ref; a.ld = io->ld; a.ws = io->ws;
+    a.cost = io->cost; a.actions_out = io->actions_out; a.plan_out = io->plan_out; a.best = io->best; a.ess = io->ess;
+    a.rows = rows;
+    a.seed = io->seed; a.call0 = io->call0;
+    a.horizon = io->horizon; a.candidates = io->candidates; a.hold = io->hold; a.problems = (int)n0;
+    for (int k = 0; k < 4; k++) {
+        a.sigma[k] = io->sigma[k];
+        a.h_a[k] = io->h_a[k];
+    }
+    a.temperature = io->temperature; a.pad_ = 0;
+    a.cfg.dt = ctx->cfg.dt; a.cfg.pad_ = 0; a.cfg.af = ctx->cfg.af;
+    a.wt = ctx->wt;
+    NP_HIP(launch_model_mppi(shape, a, (hipStream_t)stream));
     return 0;
 }
 

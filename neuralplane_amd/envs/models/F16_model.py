@@ -115,6 +115,15 @@ class F16Model(BaseModel):
                                    fanout=fanout, s_init=t(s_init), u_init=t(u_init), cost=cost, shape=shape, want_best=want_best)
         return (out[0], out[1].t(), out[2].t(), out[3].transpose(1, 2)) + out[4:]
 
+    def mppi(self, actions, sigma, temperature, cost, candidates, s=None, u=None, seed=None, call0=None, hold=1, shape='auto', want_candidates=False):
+        """One MPPI iteration — sample K candidates around the plan, fly them, cost them, re-weight — as ONE library call (F16Batch.mppi,
+        np_f16_model_mppi; Euler only), in this class's row-major layout: actions [H, P, >=4], s [P, 12], u [P, 5],
+        cost = (h_s [H, 12], h_a [4], s_ref [H, P, 12]).  This model's s / u / recent_* and the env's random stream are left as they were.
+        Returns (plan [H, P, 4], cost [P * K], best [P], ess [P][, candidates [H, P * K, 4]])."""
+        t = lambda x: None if x is None else torch.as_tensor(x, device=self._b.device).transpose(-1, -2)  # noqa: E731
+        return self._b.mppi(actions, sigma, temperature, (cost[0], cost[1], t(cost[2])), candidates, s=t(s), u=t(u), seed=seed, call0=call0, hold=hold,
+                            shape=shape, want_candidates=want_candidates)
+
     def linearize(self, s=None, u=None, want_xdot=True):
         """xdot = f(s, u), A = df/ds, B = df/du of the flight dynamics about a flight condition, per aircraft, as ONE kernel launch
         (F16Batch.linearize, np_f16_model_linearize): what trim solvers, LQR / gain scheduling, iLQR and stability analysis start from.
