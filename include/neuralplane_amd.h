@@ -757,6 +757,42 @@ NP_STATIC_ASSERT(offsetof(np_f16_mppi_io, ld) == 120 && offsetof(np_f16_mppi_io,
 NP_STATIC_ASSERT(offsetof(np_f16_mppi_io, best) == 160 && offsetof(np_f16_mppi_io, actions_out) == 176 && offsetof(np_f16_mppi_io, ws) == 184, "np_f16_mppi_io layout");
 int np_f16_model_mppi(np_f16_ctx *ctx, int64_t n0, const np_f16_mppi_io *io, void *stream);
 
+/* Batched trim (a new symbol and record within ABI 16; no earlier record changes): for each of n rows a damped Newton solve for a steady
+ * flight condition, run to convergence in ONE launch.  With z = (s[0..11], u[0..3]) and m unknowns q that move z along the columns of D,
+ *     r(z) = (xdot(z) - tgt)[rows],   phi = sum_i (r_i / scale[rows[i]])^2,   J = [A | B][rows, :] D,   J delta = -r,   z+ = clamp(z + D delta, lo, hi)
+ * xdot, A and B being np_f16_model_linearize's.  A full step is taken when phi(z+) <= (1 - 2c) phi(z), c = 1e-4; otherwise the row
+ * backtracks over alpha = 1/2 .. 1/256 and takes the largest alpha with phi <= (1 - 2 c alpha) phi(z).  A pure function: nothing of the
+ * context is written.
+ *   m in [1, 12]; D [16][12] row-major, columns m.. ignored, no column of the first m all zero (a tie such as "theta follows alpha" is a
+ *   column with two ones); rows[0..m): distinct rows of xdot; scale[12] > 0: the residuals' units; lo[16] <= hi[16]: the box trial points
+ *   are clamped to, +-inf = free (only components some column of D moves are clamped).  All of these are HOST values inside the record.
+ *   tgt [12][ld0] or NULL (zero): the prescribed xdot per row (climb rate in row 2, turn rate in row 5).
+ *   s [12][ld_out], u [5][ld_out]: the returned point (row 4 of u is u0's); res [n] = sqrt(phi) there; iters [n] (int32) = linearisations of
+ *   the row after the first; status [n] (int32): 0 converged (phi <= tol^2), 1 iteration limit, 2 line search stalled (the point is the
+ *   last one accepted), 3 singular (a pivot at most 2^-20 of its column's largest element, rows taken in units of scale), 4 non-finite:
+ *   a non-finite start returns the start with res = NaN, a non-finite iterate the last finite point accepted.
+ *   backtracks [n] (int32) or NULL: the full steps of the row the Armijo test refused (iters - backtracks = the points accepted after the start).
+ *   xdot [12][ld_out], A [144][ld_out], B [48][ld_out]: np_f16_linearize_io's, at the returned point, from one closing pass; each may be
+ *   NULL, but A and B come together; all three NULL = no closing pass.  max_iters in [0, 64]; 0 returns the start with its residual and status 1.
+ *   max_groups: as np_f16_linearize_io's.  The results do not depend on it, nor on which rows share a launch.
+ * Everything is checked on the host before the launch (np_last_error names the field).  Refused by name: a context with a fleet, with
+ * aero_gemm_order, with aero_1d_tables, and a SingleCombat context.  Euler and rk4 contexts alike: the solve works on nlplant, not on a step. */
+typedef struct np_f16_trim_io {
+    const float *s0, *u0, *tgt; int64_t ld0;    /* start [12][ld0], [5][ld0]; targets [12][ld0] or NULL */
+    float *s, *u, *res; int32_t *iters, *status, *backtracks;   /* [12][ld_out], [5][ld_out], [n], [n], [n], [n] or NULL */
+    float *xdot, *A, *B; int64_t ld_out;        /* optional: [12][ld_out], [144][ld_out], [48][ld_out] */
+    int32_t m, max_iters, max_groups, reserved_;   /* reserved_ must be 0 */
+    float tol, pad_;
+    int32_t rows[12];
+    float D[16][12];
+    float scale[12], lo[16], hi[16];
+} np_f16_trim_io;
+NP_STATIC_ASSERT(sizeof(np_f16_trim_io) == 1128, "np_f16_trim_io is 1128 bytes");
+NP_STATIC_ASSERT(offsetof(np_f16_trim_io, ld0) == 24 && offsetof(np_f16_trim_io, s) == 32 && offsetof(np_f16_trim_io, xdot) == 80 && offsetof(np_f16_trim_io, ld_out) == 104, "np_f16_trim_io layout");
+NP_STATIC_ASSERT(offsetof(np_f16_trim_io, m) == 112 && offsetof(np_f16_trim_io, tol) == 128 && offsetof(np_f16_trim_io, rows) == 136 && offsetof(np_f16_trim_io, D) == 184, "np_f16_trim_io layout");
+NP_STATIC_ASSERT(offsetof(np_f16_trim_io, scale) == 952 && offsetof(np_f16_trim_io, lo) == 1000 && offsetof(np_f16_trim_io, hi) == 1064, "np_f16_trim_io layout");
+int np_f16_model_trim(np_f16_ctx *ctx, int64_t n, const np_f16_trim_io *io, void *stream);
+
 /* Average duration in ms of the `count` most recent np_f16_step / np_f16_combat_step launches on this context, measured with
  * HIP events on the launch stream: a start / stop pair attached to each kernel's own dispatch (hipExtLaunchKernelGGL — the
  * timestamps of the kernel's packet, no extra barrier packets between back-to-back launches; 0 disables, enable with

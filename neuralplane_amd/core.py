@@ -7,6 +7,7 @@ kernels in csrc/.  State is structure-of-arrays (`s[12,n]`, `u[5,n]`, `tgt[3,n]`
 tensors the reference exposes (`model.s`, `model.u`) are transposed *views* of these buffers.
 """
 import ctypes as C
+import math
 import os
 
 import torch
@@ -93,6 +94,41 @@ def _check_airframe(sd, airframe):
 
 
 FLEET_MAX_CLASSES = 65536
+
+# F16Batch.trim: the residuals' units per row of xdot (ft/s for the position rates, 0.01 rad/s for the attitude and flow-angle rates, ft/s^2
+# for vt, 0.01 rad/s^2 for the body rates) and the default tolerance in those units: four times the fp32 evaluation error of xdot at trim (4.8e-4 of these units
+# at the worst of tests/test_gpu_trim.py's flight conditions)
+TRIM_SCALE = (1.0, 1.0, 1.0, 0.01, 0.01, 0.01, 1.0, 0.01, 0.01, 0.01, 0.01, 0.01)
+TRIM_TOL = 2e-3
+_Z = {k: i for i, k in enumerate(('npos', 'epos', 'alt', 'phi', 'theta', 'psi', 'vt', 'alpha', 'beta', 'P', 'Q', 'R', 'T', 'el', 'ail', 'rud'))}
+
+
+def trim_problem(kind, airframe=None):
+    """(unknowns [16, m], rows, scale, lo, hi) of F16Batch.trim for the usual formulations, z = (s[0..11], u[0..3]):
+      'longitudinal' (m = 3): alpha with theta tied (the flight-path angle theta - alpha of the start is kept), T, el against the rates
+                     of vt, alpha and Q (rows 6, 7, 10): wings-level flight at the start's altitude, airspeed and flight-path angle;
+      'six_dof'      (m = 6): alpha (theta tied), beta, T, el, ail, rud against rows 6..11;
+      'turn'         (m = 10): phi, theta, alpha, P, Q, R, T, el, ail, rud against rows 2..7, 9..11 and row 8, beta held: climb rate and
+                     turn rate come through trim's target (rows 2 and 5).
+    The box is the control range the env's action scaling spans (thrust from 0); states are free.  airframe: an np_f16_airframe block
+    (_lib.airframe(...)) or None = the F-16."""
+    af = _lib.airframe({'Heng': 0.0}) if airframe is None or not any(bytes(airframe)) else airframe   # the all-zero block reads as the F-16
+    t_max = af.thrust_frac * af.thrust_max / af.thrust_unit
+    cols = {'longitudinal': (('alpha', 'theta'), ('T',), ('el',)),
+            'six_dof': (('alpha', 'theta'), ('beta',), ('T',), ('el',), ('ail',), ('rud',)),
+            'turn': tuple((k,) for k in ('phi', 'theta', 'alpha', 'P', 'Q', 'R', 'T', 'el', 'ail', 'rud'))}
+    rows = {'longitudinal': [6, 7, 10], 'six_dof': [6, 7, 8, 9, 10, 11], 'turn': [2, 3, 4, 5, 6, 7, 9, 10, 11, 8]}
+    if kind not in cols:
+        raise ValueError(f'trim_problem: kind must be one of {sorted(cols)}, got {kind!r}')
+    D = torch.zeros((16, len(cols[kind])), dtype=torch.float32)
+    for j, names in enumerate(cols[kind]):
+        for k in names:
+            D[_Z[k], j] = 1.0
+    lo, hi = [-math.inf] * 16, [math.inf] * 16
+    lo[12], hi[12] = 0.0, t_max
+    for k in range(3):
+        lo[13 + k], hi[13 + k] = -af.surf_max[k], af.surf_max[k]
+    return D, rows[kind], list(TRIM_SCALE), lo, hi
 
 
 def fleet_classes(config, airframes=None):
@@ -536,6 +572,63 @@ class F16Batch:
         io.max_groups = int(max_groups)
         _lib.check(self.lib.np_f16_model_linearize(self._ctx, n0, C.byref(io), self._stream()))
         return (xdot[:, :n0] if want_xdot else None), A[:, :, :n0], B[:, :, :n0]
+
+    def trim(self, s, u, unknowns, rows, target=None, scale=None, lo=None, hi=None, tol=TRIM_TOL, max_iters=20, want_linearization=False, max_groups=0, backtracks=None):
+        """Batched trim: a damped Newton solve per row for a steady flight condition, run to convergence in ONE launch (np_f16_model_trim).
+        With z = (s[0..11], u[0..3]), the m unknowns move z along the columns of `unknowns` [16, m] (a tie such as "theta follows alpha"
+        is a column with two ones) until the rows `rows` of xdot(z) - target vanish: |r_i| in units of scale[rows[i]], merit phi the sum
+        of their squares, converged at phi <= tol^2.  Full Newton steps under an Armijo test, backtracking over 1/2 .. 1/256 where it
+        fails; trial points are clamped to [lo, hi] ([16] each, +-inf = free).  trim_problem() builds (unknowns, rows, scale, lo, hi) for
+        the usual formulations.  A pure function: the batch, s and u are left exactly as they were.
+        s [12, n0], u [5, n0]: the start; target [12, n0] or None (zero): the prescribed xdot, e.g. climb rate in row 2, turn rate in row 5.
+        Returns (s [12, n0], u [5, n0], res [n0] = sqrt(phi), iters [n0] int32, status [n0] int32 (_lib.TRIM_STATUS: 0 converged, 1 iteration
+        limit, 2 line search stalled, 3 singular, 4 non-finite)), and with want_linearization also (xdot [12, n0], A [12, 12, n0],
+        B [12, 4, n0]) at the returned point, exactly what linearize(s, u) gives there.  max_groups caps the grid (0 = auto).
+        backtracks: an int32 device tensor [n0] of the caller's that receives, per row, the full steps the Armijo test refused."""
+        if s.dim() != 2 or u.dim() != 2 or s.shape[0] != 12 or u.shape[0] != 5 or s.shape[1] != u.shape[1] or s.shape[1] < 1:
+            raise ValueError(f'trim: s must be [12, n0] and u [5, n0], got {tuple(s.shape)} and {tuple(u.shape)}')
+        s = s.to(device=self.device, dtype=torch.float32).contiguous()
+        u = u.to(device=self.device, dtype=torch.float32).contiguous()
+        n0 = int(s.shape[1])
+        D = torch.as_tensor(unknowns, dtype=torch.float32).cpu()
+        rows = [int(r) for r in rows]
+        if D.dim() != 2 or D.shape[0] != 16 or not 1 <= D.shape[1] <= 12 or len(rows) != D.shape[1]:
+            raise ValueError(f'trim: unknowns must be [16, m] with 1 <= m <= 12 and rows m rows of xdot, got {tuple(D.shape)} and {len(rows)} rows')
+        io = _lib.NpF16TrimIo()
+        io.m, io.max_iters, io.max_groups, io.tol = D.shape[1], int(max_iters), int(max_groups), float(tol)
+        for j, r in enumerate(rows):
+            io.rows[j] = r
+        for e in range(16):
+            for j in range(D.shape[1]):
+                io.D[e][j] = float(D[e, j])
+        for name, given, default, k in (('scale', scale, 1.0, 12), ('lo', lo, -math.inf, 16), ('hi', hi, math.inf, 16)):
+            vals = [default] * k if given is None else [float(x) for x in given]
+            if len(vals) != k:
+                raise ValueError(f'trim: {name} must have {k} entries, got {len(vals)}')
+            for e in range(k):
+                getattr(io, name)[e] = vals[e]
+        if target is not None:
+            if target.dim() != 2 or tuple(target.shape) != (12, n0):
+                raise ValueError(f'trim: target must be [12, n0 = {n0}], got {tuple(target.shape)}')
+            target = target.to(device=self.device, dtype=torch.float32).contiguous()
+            io.tgt = target.data_ptr()
+        io.s0, io.u0, io.ld0 = s.data_ptr(), u.data_ptr(), n0
+        s_out, u_out = torch.empty_like(s), torch.empty_like(u)
+        res = torch.empty((n0,), dtype=torch.float32, device=self.device)
+        iters = torch.empty((n0,), dtype=torch.int32, device=self.device)
+        status = torch.empty((n0,), dtype=torch.int32, device=self.device)
+        io.s, io.u, io.res, io.iters, io.status, io.ld_out = s_out.data_ptr(), u_out.data_ptr(), res.data_ptr(), iters.data_ptr(), status.data_ptr(), n0
+        if backtracks is not None:
+            if backtracks.dtype != torch.int32 or backtracks.device != s.device or tuple(backtracks.shape) != (n0,) or not backtracks.is_contiguous():
+                raise ValueError(f'trim: backtracks must be a contiguous int32 tensor [n0 = {n0}] on {s.device}')
+            io.backtracks = backtracks.data_ptr()
+        lin = ()
+        if want_linearization:
+            lin = (torch.empty((12, n0), dtype=torch.float32, device=self.device), torch.empty((12, 12, n0), dtype=torch.float32, device=self.device),
+                   torch.empty((12, 4, n0), dtype=torch.float32, device=self.device))
+            io.xdot, io.A, io.B = (x.data_ptr() for x in lin)
+        _lib.check(self.lib.np_f16_model_trim(self._ctx, n0, C.byref(io), self._stream()))
+        return (s_out, u_out, res, iters, status) + lin
 
     def rollout_vjp(self, actions, s_traj, g_s_traj, g_u_end=None, s=None, u=None, fanout=1, horizon=None, max_groups=0, ld_out=None):
         """The vector-Jacobian product of rollout(actions, s, u, fanout, record_every=1) as ONE launch (np_f16_model_rollout_vjp; Euler only):

@@ -514,6 +514,54 @@ inline const char *linearize_context_error(bool combat, bool fleet, bool gemm_or
     return nullptr;
 }
 
+// ---- np_f16_model_trim (np_model_trim.hip) --------------------------------------------------------------------------------------------
+// The record of a trim of n rows, checked before anything is launched: null, or the first thing wrong with it.  D, rows, scale, lo and hi
+// are host values inside the record.  The row limits are the linearisation's; the grid is linearize_groups of n rows.
+constexpr int32_t TRIM_ITERS_LIMIT = 64, TRIM_M_LIMIT = 12;
+inline const char *trim_io_error(int64_t n, const np_f16_trim_io *io) {
+    if (!io) return "np_f16_model_trim: null io";
+    const int64_t lim = 1ll << 30;
+    if (n < 1 || n >= lim) return "np_f16_model_trim: n must be at least 1 and below 2^30";
+    if (io->m < 1 || io->m > TRIM_M_LIMIT) return "np_f16_model_trim: m must be in [1, 12]";
+    if (io->max_iters < 0 || io->max_iters > TRIM_ITERS_LIMIT) return "np_f16_model_trim: max_iters must be in [0, 64]";
+    if (!(io->tol > 0.0f) || !(io->tol - io->tol == 0.0f)) return "np_f16_model_trim: tol must be positive and finite";
+    for (int i = 0; i < io->m; i++) {
+        if (io->rows[i] < 0 || io->rows[i] > 11) return "np_f16_model_trim: rows must be rows 0..11 of xdot";
+        for (int j = 0; j < i; j++)
+            if (io->rows[j] == io->rows[i]) return "np_f16_model_trim: rows must be distinct";
+    }
+    for (int j = 0; j < io->m; j++) {
+        bool any = false;
+        for (int e = 0; e < 16; e++) {
+            if (!(io->D[e][j] - io->D[e][j] == 0.0f)) return "np_f16_model_trim: D must be finite";
+            any = any || io->D[e][j] != 0.0f;
+        }
+        if (!any) return "np_f16_model_trim: a column of D is all zero (the unknown moves nothing)";
+    }
+    for (int k = 0; k < 12; k++)
+        if (!(io->scale[k] > 0.0f) || !(io->scale[k] - io->scale[k] == 0.0f)) return "np_f16_model_trim: scale must be positive and finite";
+    for (int e = 0; e < 16; e++)
+        if (!(io->lo[e] <= io->hi[e])) return "np_f16_model_trim: lo must not exceed hi (and neither may be NaN)";
+    if (!io->s0 || !io->u0) return "np_f16_model_trim: null start (s0, u0)";
+    if (!io->s || !io->u) return "np_f16_model_trim: null output (s, u)";
+    if (!io->res || !io->iters || !io->status) return "np_f16_model_trim: null output (res, iters, status)";
+    if ((io->A == nullptr) != (io->B == nullptr)) return "np_f16_model_trim: A and B come together (or neither)";
+    if (io->ld0 < n || io->ld0 >= lim) return "np_f16_model_trim: ld0 must be at least n and below 2^30";
+    if (io->ld_out < n || io->ld_out >= lim) return "np_f16_model_trim: ld_out must be at least n and below 2^30";
+    if (io->max_groups < 0) return "np_f16_model_trim: max_groups must not be negative";
+    if (io->reserved_ != 0) return "np_f16_model_trim: reserved_ must be 0";
+    return nullptr;
+}
+
+// Contexts the trim kernel is not built for: null, or the refusal, by name (the solver does not matter: the solve works on nlplant)
+inline const char *trim_context_error(bool combat, bool fleet, bool gemm_order, bool tables) {
+    if (combat) return "np_f16_model_trim: a SingleCombat context has no trim kernel (create the context with np_f16_ctx_create)";
+    if (fleet) return "np_f16_model_trim: a context with a fleet has no trim kernel (it reads one airframe per context)";
+    if (gemm_order) return "np_f16_model_trim: a context with aero_gemm_order has no trim kernel (built for the default order of the aero nets)";
+    if (tables) return "np_f16_model_trim: a context with aero_1d_tables has no trim kernel (built for the MLP numerics)";
+    return nullptr;
+}
+
 // ---- np_f16_model_rollout_vjp (np_model_rollout_vjp.hip) ----------------------------------------------------------------------------
 // The record of a reverse sweep over n0 start rows, checked before anything is launched: null, or the first thing wrong with it.  The
 // limits are the rollout's (rows of every array are a 64-bit base + a 32-bit byte offset); the grid is linearize_groups of n0 * fanout rows.

@@ -35,6 +35,7 @@
 #include "np_model_ilqr.h"
 #include "np_model_rollout_fb.h"
 #include "np_model_mppi.h"
+#include "np_model_trim.h"
 namespace npact8 {
 hipError_t launch_actor_i8(const float *weights, long long n, const float *obs, const float *h_in, const float *masks, float *actions, float *h_out,
                            hipStream_t stream);   // np_actor_i8.hip
@@ -1682,6 +1683,47 @@ int np_f16_model_mppi(np_f16_ctx *ctx, int64_t n0, const np_f16_mppi_io *io, voi
     a.cfg.dt = ctx->cfg.dt; a.cfg.pad_ = 0; a.cfg.af = ctx->cfg.af;
     a.wt = ctx->wt;
     NP_HIP(launch_model_mppi(shape, a, (hipStream_t)stream));
+    return 0;
+}
+
+// Batched trim in one launch (np_model_trim.hip).  As its siblings: the record first, then the context; nothing is touched, and no device
+// call is made, before every refusal has had its turn.  D, rows, scale and the box travel in the kernel's argument record.
+static_assert(TRIM_ITERS_LIMIT == TRIM_MAX_ITERS && TRIM_M_LIMIT == TRIM_MAX_M, "np_f16_host.h mirrors np_model_trim.h");
+int np_f16_model_trim(np_f16_ctx *ctx, int64_t n, const np_f16_trim_io *io, void *stream) {
+    if (const char *e = trim_io_error(n, io)) return fail(e);
+    if (!ctx) return fail("np_f16_model_trim: null ctx");
+    if (const char *e = trim_context_error(ctx->combat, ctx->fleet_k > 0, ctx->gemm_order, !ctx->combat && ctx->cfg.aero_1d_tables != 0)) return fail(e);
+    int32_t groups = 0;
+    if (const char *e = linearize_groups(n, ctx->num_cus, io->max_groups, &groups)) return fail(e);
+    DeviceGuard guard;
+    NP_HIP(guard.enter(ctx->device));
+    TrimArgs a;
+    a.s0 = io->s0; a.u0 = io->u0; a.tgt = io->tgt; a.ld0 = io->ld0;
+    a.s = io->s; a.u = io->u; a.res = io->res; a.iters = io->iters; a.status = io->status; a.backtracks = io->backtracks;
+    a.xdot = io->xdot; a.A = io->A; a.B = io->B; a.ld_out = io->ld_out;
+    a.rows = n;
+    a.kblob = ctx->wt.kblob;
+    a.m = io->m; a.max_iters = io->max_iters; a.tol2 = io->tol * io->tol; a.pad_ = 0.0f;
+    for (int k = 0; k < 12; k++) {
+        a.slot_of[k] = -1;
+        a.scale[k] = io->scale[k];
+        a.row_of[k] = 0;
+    }
+    for (int i = 0; i < io->m; i++) {
+        a.row_of[i] = io->rows[i];
+        a.slot_of[io->rows[i]] = i;
+    }
+    for (int e = 0; e < TRIM_Z; e++) {
+        bool moves = false;
+        for (int j = 0; j < TRIM_MAX_M; j++) {
+            a.D[e][j] = j < io->m ? io->D[e][j] : 0.0f;
+            moves = moves || a.D[e][j] != 0.0f;
+        }
+        a.lo[e] = moves ? io->lo[e] : -INFINITY;   // a component no unknown moves is the caller's: never clamped
+        a.hi[e] = moves ? io->hi[e] : INFINITY;
+    }
+    a.af = ctx->cfg.af;
+    NP_HIP(launch_model_trim(groups, a, (hipStream_t)stream));
     return 0;
 }
 

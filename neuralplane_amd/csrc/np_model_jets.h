@@ -250,6 +250,85 @@ __device__ __forceinline__ void eval_plan_jet(const float *blob, const float (&x
 #undef NPF16_ITEM
 }
 
+// ---- the same nets by value only (np_model_trim.hip's backtracking pass): the value chains above, operation for operation and in the same
+// order (bias first, k ascending; the output layer's two interleaved partial chains), without the tangent chains beside them.  The reads
+// and FMAs are ordered by the same two chain values.  The value of slot `slot` goes where eval_class_jet puts it, column lin_col(slot); the
+// derivative columns are left as they are (nobody reads them after a value pass) ----
+template <int OUT>
+__device__ __forceinline__ void tie_val(LdsRec &ws, int which, const float (&y)[OUT]) {
+    static_assert(OUT % 5 == 0, "layer widths are multiples of five");
+#pragma unroll
+    for (int j = 0; j < OUT; j += 5) asm volatile("" : "+v"(ws.chain[which]) : "v"(y[j]), "v"(y[j + 1]), "v"(y[j + 2]), "v"(y[j + 3]), "v"(y[j + 4]));
+}
+template <int BASE, int IN, int OUT>
+__device__ __forceinline__ void dense_val(LdsRec &ws, const float (&x)[IN], float (&y)[OUT]) {
+    const auto bias = ws.template row<OUT>(BASE);
+#pragma unroll
+    for (int j = 0; j < OUT; j++) y[j] = bias[BASE + j];
+#pragma unroll
+    for (int k = 0; k < IN; k++) {
+        const int p0 = BASE + (1 + k) * pad2(OUT);
+        const auto wk = ws.template row<OUT>(p0, k & 1);
+#pragma unroll
+        for (int j = 0; j < OUT; j++) y[j] = fmaf(wk[p0 + j], x[k], y[j]);
+        tie_val<OUT>(ws, k & 1, y);
+    }
+#pragma unroll
+    for (int j = 0; j < OUT; j++) {
+        y[j] = y[j] > 0.0f ? y[j] : 0.0f;
+        y[j] = y[j] > 1.0f ? 1.0f : y[j];
+    }
+}
+template <int BASE, int IN>
+__device__ __forceinline__ float out_val(LdsRec &ws, const float (&x)[IN]) {
+    const auto r = ws.template row<4 + pad2(IN)>(BASE);  // the layer, then out_std and out_mean
+    float lo = r[BASE], hi = r[BASE + 1];
+#pragma unroll
+    for (int k = 0; k + 1 < IN; k += 2) {
+        lo = fmaf(r[BASE + 2 + k], x[k], lo);
+        hi = fmaf(r[BASE + 3 + k], x[k + 1], hi);
+    }
+    if (IN & 1) lo = fmaf(r[BASE + 2 + IN - 1], x[IN - 1], lo);
+    return (lo + hi) * r[BASE + 2 + pad2(IN)] + r[BASE + 3 + pad2(IN)];  // unnormalize: X * std + mean
+}
+template <int IN, int H1, int H2, int H3>
+__device__ __forceinline__ float net_val(LdsRec &ws, const float (&x)[IN]) {
+    constexpr int B2 = dense_len(IN, H1), B3 = B2 + dense_len(H1, H2), BO = H3 > 0 ? B3 + dense_len(H2, H3) : B3;
+    float h1[H1], h2[H2];
+    dense_val<0, IN, H1>(ws, x, h1);
+    dense_val<B2, H1, H2>(ws, h1, h2);
+    if constexpr (H3 > 0) {
+        float h3[H3];
+        dense_val<B3, H2, H3>(ws, h2, h3);
+        return out_val<BO, H3>(ws, h3);
+    } else {
+        return out_val<BO, H2>(ws, h2);
+    }
+}
+template <int CL, int FIRST, int COUNT>
+__device__ __forceinline__ void eval_class_val(LdsRec &ws, const float (&xn)[NUM_NORM_GROUPS], float *col) {
+    constexpr NetClass c = CLASSES[CL];
+    float x[c.n_in];
+#pragma unroll
+    for (int k = 0; k < c.n_in; k++) x[k] = xn[c.grp[k]];
+#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
+    for (int i = 0; i < COUNT; i++) {
+        ws.rec = (class_base(CL) + (FIRST + i) * class_stride(CL)) / 4;
+        col[(lin_col(class_slot(CL) + FIRST) + i * (1 + c.n_in)) * LIN_TILE] = net_val<c.n_in, c.h1, c.h2, c.h3>(ws, x);
+    }
+}
+template <int W>
+__device__ __forceinline__ void eval_plan_val(const float *blob, const float (&xn)[NUM_NORM_GROUPS], float *col) {
+    LdsRec ws = {(const f32x4 *)blob, 0, {0, 0}};
+#define NPF16_ITEM(K) \
+    if constexpr (PLAN8_LIN.it[W][K].cnt > 0) eval_class_val<PLAN8_LIN.it[W][K].cl, PLAN8_LIN.it[W][K].first, PLAN8_LIN.it[W][K].cnt>(ws, xn, col)
+    NPF16_ITEM(0);
+    NPF16_ITEM(1);
+    NPF16_ITEM(2);
+    NPF16_ITEM(3);
+#undef NPF16_ITEM
+}
+
 // ---- phase 2: value + N tangents.  The value halves are the spec's operations, one for one; the tangents are the chain rule ----------------
 template <int N>
 struct Jet {

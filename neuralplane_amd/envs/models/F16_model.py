@@ -137,6 +137,15 @@ class F16Model(BaseModel):
         xdot, A, B = self._b.linearize(s, u, want_xdot=want_xdot)
         return (xdot.t() if xdot is not None else None), A.permute(2, 0, 1), B.permute(2, 0, 1)
 
+    def trim(self, s, u, unknowns, rows, target=None, **kw):
+        """Batched trim — a damped Newton solve per aircraft for a steady flight condition, run to convergence in ONE kernel launch
+        (F16Batch.trim, np_f16_model_trim; core.trim_problem builds unknowns / rows / scale / lo / hi), in this class's row-major layout:
+        s [n0, 12], u [n0, 5], target [n0, 12].  This model's s / u / recent_* are left exactly as they were.
+        Returns (s [n0, 12], u [n0, 5], res [n0], iters [n0], status [n0][, xdot [n0, 12], A [n0, 12, 12], B [n0, 12, 4]]) — views."""
+        t = lambda x: None if x is None else torch.as_tensor(x, device=self._b.device).t()  # noqa: E731
+        out = self._b.trim(t(s), t(u), unknowns, rows, target=t(target), **kw)
+        return (out[0].t(), out[1].t()) + out[2:5] + ((out[5].t(), out[6].permute(2, 0, 1), out[7].permute(2, 0, 1)) if len(out) > 5 else ())
+
     def get_extended_state(self):
         """nlplant(hstack(s,u)) — reference returns [n,17] with zero control derivatives (F16_model.py:47-49)."""
         d = self._b.derived()
