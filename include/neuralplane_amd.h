@@ -793,6 +793,48 @@ NP_STATIC_ASSERT(offsetof(np_f16_trim_io, m) == 112 && offsetof(np_f16_trim_io, 
 NP_STATIC_ASSERT(offsetof(np_f16_trim_io, scale) == 952 && offsetof(np_f16_trim_io, lo) == 1000 && offsetof(np_f16_trim_io, hi) == 1064, "np_f16_trim_io layout");
 int np_f16_model_trim(np_f16_ctx *ctx, int64_t n, const np_f16_trim_io *io, void *stream);
 
+/* Batched LQR (a new symbol and record within ABI 16; no earlier record changes): for each of n rows the steady-state gain of the `update`
+ * step map at the caller's (A, B), by solving the discrete algebraic Riccati equation with the structured doubling algorithm, run to
+ * convergence in ONE launch.  No nets are evaluated.  Coordinates are np_f16_ilqr_io's, x = (s[12], u[0:4]): K is what np_f16_feedback_io.K
+ * consumes.  With the context's dt, kappa = the lag's keep factor and gain_k = d u'[k] / d a[k],
+ *     Phi = [[I + dt A, dt B], [0, I]],   S = diag(1 x 12, kappa x 4),   D = diag(gain_k)
+ * (D takes no clamp: an operating point's actions are interior) and M = diag(select), bit i of select = coordinate i takes part,
+ *     A_d = M Phi S M,   B_d = M Phi[:, 12:16] D,   Q = M diag(h_s[12], 0 x 4) M,   R = diag(h_a[4]).
+ * Unselected coordinates get exactly zero gain columns and zero rows and columns of P: drop the position and heading integrators, or design
+ * a longitudinal regulator only.  Equilibration: the recursion runs in x = T x~, T = diag(t) of powers of two shared by the rows (exact in
+ * fp32): t_i = 2^rint(log2(1 / sqrt(h_s[i]))) for a selected state with h_s[i] > 0, t_(12+k) = 2^rint(log2(gain_k / sqrt(h_a[k]))), 1
+ * elsewhere, exponents held to +-40; A_d <- T^-1 A_d T, B_d <- T^-1 B_d, Q <- T Q T on entry, K <- K T^-1, P <- T^-1 H T^-1 on exit.  In
+ * exact arithmetic nothing changes; in fp32 the pivots of the solve below are chosen among comparable numbers.
+ * The doubling starts from A_0 = A_d, G_0 = B_d R^-1 B_d^T, H_0 = Q and computes
+ *     W = I + G H,   X = W^-1 A,   Y = W^-1 G   (Gauss-Jordan, partial pivoting),   A+ = A X,   G+ = sym(G + A Y A^T),   H+ = sym(H + A^T H X):
+ * H after j doublings is the value Hessian that step 0 of a 2^j-step sweep of np_f16_ilqr_io consumes (constant Phi and h_s, mu = 0, the
+ * stage cost added).  It stops at the first doubling with max over (i, j), H+_ii H+_jj > 0, of |H+_ij - H_ij| / sqrt(H+_ii H+_jj) <= tol,
+ * otherwise at max_doublings (0..32); a doubling whose result is not finite in fp32 (a diverging recursion: an unstable mode that B_d does
+ * not reach) is not taken and ends the row as the limit does.
+ *   K [64][ld_out], plane 16 a + j:  K = -(R + B_d^T H B_d)^-1 B_d^T H A_d, by np_f16_ilqr_io's square-root-free 4 x 4 LDL^T.
+ *   P [256][ld_out], plane 16 i + j, or NULL: H itself, the fixed point of the standard DARE of (A_d, B_d, Q, R).
+ *   doublings [n] (int32): the doublings taken;  res [n]: the last value of the criterion (+inf when none was taken).
+ *   status [n] (int32): 0 converged; 1 limit reached (K and P are those of the last H, a valid 2^doublings-step gain); 3 a pivot was
+ *   rejected (of the W solve: |p| <= 2^-20 of the largest element of its column of W; of the LDL^T: not positive or not finite), outputs 0;
+ *   4 non-finite A or B (or an A_d, G_0 beyond fp32's range), outputs NaN.  Neighbours of a bad row are untouched in every case.
+ *   A [12][12][ld], B [12][4][ld]: planar, exactly what np_f16_model_linearize and np_f16_model_trim return.  h_s, h_a, select: HOST values.
+ *   max_groups: caps the grid (0 = auto).  The results do not depend on it, nor on which rows share a launch.
+ * Everything is checked on the host before the launch (np_last_error names the field): h_s finite and >= 0, h_a finite and > 0, tol finite
+ * and > 0, max_doublings in [0, 32], select within 16 bits, the pitches at least n.  Refused by name: an rk4 context (the step map is the
+ * Euler step's), a context with a fleet, a SingleCombat context.  cfg.airframe's control scales are honoured.  A pure function: nothing of
+ * the context is written. */
+typedef struct np_f16_lqr_io {
+    const float *A, *B; int64_t ld;             /* [144][ld], [48][ld] */
+    float *K, *P; int32_t *doublings; float *res; int32_t *status; int64_t ld_out;   /* [64][ld_out], [256][ld_out] or NULL, [n], [n], [n] */
+    int32_t select, max_doublings, max_groups, reserved_;   /* reserved_ must be 0 */
+    float tol;
+    float h_s[12], h_a[4];
+} np_f16_lqr_io;
+NP_STATIC_ASSERT(sizeof(np_f16_lqr_io) == 160, "np_f16_lqr_io is 160 bytes");
+NP_STATIC_ASSERT(offsetof(np_f16_lqr_io, ld) == 16 && offsetof(np_f16_lqr_io, K) == 24 && offsetof(np_f16_lqr_io, doublings) == 40 && offsetof(np_f16_lqr_io, ld_out) == 64, "np_f16_lqr_io layout");
+NP_STATIC_ASSERT(offsetof(np_f16_lqr_io, select) == 72 && offsetof(np_f16_lqr_io, max_doublings) == 76 && offsetof(np_f16_lqr_io, tol) == 88 && offsetof(np_f16_lqr_io, h_s) == 92 && offsetof(np_f16_lqr_io, h_a) == 140, "np_f16_lqr_io layout");
+int np_f16_model_lqr(np_f16_ctx *ctx, int64_t n, const np_f16_lqr_io *io, void *stream);
+
 /* Average duration in ms of the `count` most recent np_f16_step / np_f16_combat_step launches on this context, measured with
  * HIP events on the launch stream: a start / stop pair attached to each kernel's own dispatch (hipExtLaunchKernelGGL — the
  * timestamps of the kernel's packet, no extra barrier packets between back-to-back launches; 0 disables, enable with

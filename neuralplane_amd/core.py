@@ -100,6 +100,13 @@ FLEET_MAX_CLASSES = 65536
 # at the worst of tests/test_gpu_trim.py's flight conditions)
 TRIM_SCALE = (1.0, 1.0, 1.0, 0.01, 0.01, 0.01, 1.0, 0.01, 0.01, 0.01, 0.01, 0.01)
 TRIM_TOL = 2e-3
+# F16Batch.lqr: masks over x = (s[12], u[0:4]), and the default tolerance of the stopping criterion (a relative change of the value Hessian:
+# the criterion falls quadratically, 1e-1 -> 3e-5 -> 0 on the rows of tests/test_gpu_lqr.py, and has no rounding plateau above 0 because
+# A_k underflows; 2e-5 is 10 x 16 fp32 roundings, the error of one 16-term entry of H+ - H)
+LQR_ALL = 0xFFFF
+LQR_NO_POSITION_HEADING = 0xFFFF & ~0b100011
+LQR_LONGITUDINAL = sum(1 << k for k in (2, 4, 6, 7, 10, 12, 13))
+LQR_TOL = 2e-5
 _Z = {k: i for i, k in enumerate(('npos', 'epos', 'alt', 'phi', 'theta', 'psi', 'vt', 'alpha', 'beta', 'P', 'Q', 'R', 'T', 'el', 'ail', 'rud'))}
 
 
@@ -629,6 +636,39 @@ class F16Batch:
             io.xdot, io.A, io.B = (x.data_ptr() for x in lin)
         _lib.check(self.lib.np_f16_model_trim(self._ctx, n0, C.byref(io), self._stream()))
         return (s_out, u_out, res, iters, status) + lin
+
+    def lqr(self, A, B, h_s, h_a, select=LQR_ALL, tol=LQR_TOL, max_doublings=24, want_P=False, max_groups=0):
+        """Batched LQR: per row the steady-state gain of the update() step map at an operating point's (A, B), by the structured doubling
+        algorithm for the discrete algebraic Riccati equation, run to convergence in ONE launch (np_f16_model_lqr; Euler only; no nets are
+        evaluated).  A [12, 12, n0], B [12, 4, n0]: what linearize and trim(want_linearization=True) return.  x = (s[12], u[0:4]), the
+        coordinates of ilqr_backward: the cost is sum_t x^T diag(h_s, 0) x + a^T diag(h_a) a over a_t = K x_t, with the lag and the control
+        scales of update() in the step map.  select: a 16-bit mask of the coordinates that take part (LQR_NO_POSITION_HEADING drops npos,
+        epos and psi, whose integrators no cost on the other states can stabilise; LQR_LONGITUDINAL keeps alt, theta, vt, alpha, Q, T, el);
+        the others get exactly zero gain columns and zero rows and columns of P.
+        Returns (K [4, 16, n0] — ilqr_forward's K for every step —, doublings [n0] int32, res [n0], status [n0] int32 (_lib.LQR_STATUS:
+        0 converged, 1 doubling limit: the gain of a 2^doublings-step horizon, 3 pivot rejected: zeros, 4 non-finite A or B: NaN)[, P
+        [16, 16, n0] with want_P: the value Hessian, the DARE's fixed point]).  A pure function: the batch is left exactly as it was."""
+        if A.dim() != 3 or B.dim() != 3 or tuple(A.shape[:2]) != (12, 12) or tuple(B.shape[:2]) != (12, 4) or A.shape[2] != B.shape[2] or A.shape[2] < 1:
+            raise ValueError(f'lqr: A must be [12, 12, n0] and B [12, 4, n0], got {tuple(A.shape)} and {tuple(B.shape)}')
+        A = A.to(device=self.device, dtype=torch.float32).contiguous()
+        B = B.to(device=self.device, dtype=torch.float32).contiguous()
+        n0 = int(A.shape[2])
+        h_s = [float(x) for x in torch.as_tensor(h_s).reshape(-1).tolist()]
+        h_a = [float(x) for x in torch.as_tensor(h_a).reshape(-1).tolist()]
+        if len(h_s) != 12 or len(h_a) != 4:
+            raise ValueError(f'lqr: h_s must have 12 entries and h_a 4, got {len(h_s)} and {len(h_a)}')
+        io = _lib.NpF16LqrIo()
+        io.A, io.B, io.ld = A.data_ptr(), B.data_ptr(), n0
+        io.select, io.max_doublings, io.max_groups, io.tol = int(select), int(max_doublings), int(max_groups), float(tol)
+        io.h_s, io.h_a = (C.c_float * 12)(*h_s), (C.c_float * 4)(*h_a)
+        K = torch.empty((4, 16, n0), dtype=torch.float32, device=self.device)
+        P = torch.empty((16, 16, n0), dtype=torch.float32, device=self.device) if want_P else None
+        doublings = torch.empty((n0,), dtype=torch.int32, device=self.device)
+        status = torch.empty((n0,), dtype=torch.int32, device=self.device)
+        res = torch.empty((n0,), dtype=torch.float32, device=self.device)
+        io.K, io.P, io.doublings, io.res, io.status, io.ld_out = K.data_ptr(), (P.data_ptr() if want_P else None), doublings.data_ptr(), res.data_ptr(), status.data_ptr(), n0
+        _lib.check(self.lib.np_f16_model_lqr(self._ctx, n0, C.byref(io), self._stream()))
+        return (K, doublings, res, status) + ((P,) if want_P else ())
 
     def rollout_vjp(self, actions, s_traj, g_s_traj, g_u_end=None, s=None, u=None, fanout=1, horizon=None, max_groups=0, ld_out=None):
         """The vector-Jacobian product of rollout(actions, s, u, fanout, record_every=1) as ONE launch (np_f16_model_rollout_vjp; Euler only):

@@ -562,6 +562,51 @@ inline const char *trim_context_error(bool combat, bool fleet, bool gemm_order, 
     return nullptr;
 }
 
+// ---- np_f16_model_lqr (np_model_lqr.hip) -----------------------------------------------------------------------------------------------
+// The record of a batched LQR of n rows, checked before anything is launched: null, or the first thing wrong with it.  h_s, h_a and
+// select are host values inside the record.  Planes are 64-bit arithmetic in the kernel; the row limits are the linearisation's.
+constexpr int32_t LQR_DOUBLINGS_LIMIT = 32;
+inline const char *lqr_io_error(int64_t n, const np_f16_lqr_io *io) {
+    if (!io) return "np_f16_model_lqr: null io";
+    const int64_t lim = 1ll << 30;
+    if (n < 1 || n >= lim) return "np_f16_model_lqr: n must be at least 1 and below 2^30";
+    for (int k = 0; k < 12; k++)
+        if (!(io->h_s[k] >= 0.0f) || !(io->h_s[k] - io->h_s[k] == 0.0f)) return "np_f16_model_lqr: h_s must be finite and not negative";
+    for (int k = 0; k < 4; k++)
+        if (!(io->h_a[k] > 0.0f) || !(io->h_a[k] - io->h_a[k] == 0.0f)) return "np_f16_model_lqr: h_a must be finite and positive";
+    if (!(io->tol > 0.0f) || !(io->tol - io->tol == 0.0f)) return "np_f16_model_lqr: tol must be positive and finite";
+    if (io->max_doublings < 0 || io->max_doublings > LQR_DOUBLINGS_LIMIT) return "np_f16_model_lqr: max_doublings must be in [0, 32]";
+    if (io->select < 0 || io->select > 0xFFFF) return "np_f16_model_lqr: select must be a mask of the 16 coordinates";
+    if (!io->A || !io->B) return "np_f16_model_lqr: null input (A, B)";
+    if (!io->K || !io->doublings || !io->res || !io->status) return "np_f16_model_lqr: null output (K, doublings, res, status)";
+    if (io->ld < n || io->ld >= lim) return "np_f16_model_lqr: ld must be at least n and below 2^30";
+    if (io->ld_out < n || io->ld_out >= lim) return "np_f16_model_lqr: ld_out must be at least n and below 2^30";
+    if (io->max_groups < 0) return "np_f16_model_lqr: max_groups must not be negative";
+    if (io->reserved_ != 0) return "np_f16_model_lqr: reserved_ must be 0";
+    return nullptr;
+}
+
+// Contexts whose step map is not the one the DARE is written for: null, or the refusal, by name
+inline const char *lqr_context_error(bool combat, bool fleet, int32_t solver) {
+    if (combat) return "np_f16_model_lqr: a SingleCombat context has no model kernels (create the context with np_f16_ctx_create)";
+    if (fleet) return "np_f16_model_lqr: a context with a fleet has no LQR (the control scales are one airframe's per context)";
+    if (solver != 0) return "np_f16_model_lqr: solver: rk4 has no LQR (the step map is the Euler step's)";
+    return nullptr;
+}
+
+// The equilibration x = T x~ of np_f16_lqr_io: t[16] and 1 / t, powers of two with exponents in [-40, 40]
+inline void lqr_equilibration(const np_f16_lqr_io *io, const float (&gain)[4], float (&t)[16], float (&tinv)[16]) {
+    for (int i = 0; i < 16; i++) {
+        double x = 1.0;
+        if (i < 12 && ((io->select >> i) & 1) && io->h_s[i] > 0.0f) x = 1.0 / std::sqrt((double)io->h_s[i]);
+        if (i >= 12 && gain[i - 12] > 0.0f) x = (double)gain[i - 12] / std::sqrt((double)io->h_a[i - 12]);
+        double e = std::nearbyint(std::log2(x));
+        e = e < -40.0 ? -40.0 : (e > 40.0 ? 40.0 : e);
+        t[i] = (float)std::exp2(e);
+        tinv[i] = (float)std::exp2(-e);
+    }
+}
+
 // ---- np_f16_model_rollout_vjp (np_model_rollout_vjp.hip) ----------------------------------------------------------------------------
 // The record of a reverse sweep over n0 start rows, checked before anything is launched: null, or the first thing wrong with it.  The
 // limits are the rollout's (rows of every array are a 64-bit base + a 32-bit byte offset); the grid is linearize_groups of n0 * fanout rows.

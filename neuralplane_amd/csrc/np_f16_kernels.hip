@@ -36,6 +36,7 @@
 #include "np_model_rollout_fb.h"
 #include "np_model_mppi.h"
 #include "np_model_trim.h"
+#include "np_model_lqr.h"
 namespace npact8 {
 hipError_t launch_actor_i8(const float *weights, long long n, const float *obs, const float *h_in, const float *masks, float *actions, float *h_out,
                            hipStream_t stream);   // np_actor_i8.hip
@@ -1724,6 +1725,36 @@ int np_f16_model_trim(np_f16_ctx *ctx, int64_t n, const np_f16_trim_io *io, void
     }
     a.af = ctx->cfg.af;
     NP_HIP(launch_model_trim(groups, a, (hipStream_t)stream));
+    return 0;
+}
+
+// Batched LQR in one launch (np_model_lqr.hip).  As its siblings: the record first, then the context; nothing is touched, and no device
+// call is made, before every refusal has had its turn.  The step map's constants, the weights and the equilibration travel in the kernel's
+// argument record.
+static_assert(LQR_DOUBLINGS_LIMIT == LQR_MAX_DOUBLINGS, "np_f16_host.h mirrors np_model_lqr.h");
+int np_f16_model_lqr(np_f16_ctx *ctx, int64_t n, const np_f16_lqr_io *io, void *stream) {
+    if (const char *e = lqr_io_error(n, io)) return fail(e);
+    if (!ctx) return fail("np_f16_model_lqr: null ctx");
+    if (const char *e = lqr_context_error(ctx->combat, ctx->fleet_k > 0, ctx->solver)) return fail(e);
+    DeviceGuard guard;
+    NP_HIP(guard.enter(ctx->device));
+    const Airframe &af = ctx->cfg.af;
+    LqrArgs a;
+    a.A = io->A; a.B = io->B; a.ld = io->ld;
+    a.K = io->K; a.P = io->P; a.doublings = io->doublings; a.status = io->status; a.res = io->res; a.ld_out = io->ld_out;
+    a.rows = n;
+    a.select = io->select; a.max_doublings = io->max_doublings;
+    a.tol = io->tol; a.dt = ctx->cfg.dt; a.kappa = af.lag_keep;
+    float gain[4];   // control_lag's second term at action 1, as np_model_ilqr.hip forms it
+    gain[0] = (((af.lag_new * 1.0f) * af.thrust_frac) * af.thrust_max) / af.thrust_unit;
+    for (int k = 1; k < 4; k++) gain[k] = (af.lag_new * 1.0f) * af.surf_max[k - 1];
+    lqr_equilibration(io, gain, a.t, a.tinv);
+    for (int k = 0; k < 4; k++) {
+        a.gain[k] = gain[k];
+        a.h_a[k] = io->h_a[k];
+    }
+    for (int i = 0; i < 16; i++) a.q[i] = (i < 12 && ((io->select >> i) & 1)) ? (io->h_s[i] * a.t[i]) * a.t[i] : 0.0f;
+    NP_HIP(launch_model_lqr(lqr_groups(n, ctx->num_cus, io->max_groups), a, (hipStream_t)stream));
     return 0;
 }
 

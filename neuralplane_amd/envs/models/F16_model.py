@@ -146,6 +146,15 @@ class F16Model(BaseModel):
         out = self._b.trim(t(s), t(u), unknowns, rows, target=t(target), **kw)
         return (out[0].t(), out[1].t()) + out[2:5] + ((out[5].t(), out[6].permute(2, 0, 1), out[7].permute(2, 0, 1)) if len(out) > 5 else ())
 
+    def lqr(self, A, B, h_s, h_a, **kw):
+        """Batched LQR — the steady-state gain of the update() step map at each operating point's (A, B), the discrete algebraic Riccati
+        equation solved by structured doubling in ONE kernel launch (F16Batch.lqr, np_f16_model_lqr), in this class's row-major layout:
+        A [n0, 12, 12], B [n0, 12, 4] as linearize / trim return them.  This model's s / u / recent_* are left exactly as they were.
+        Returns (K [n0, 4, 16], doublings [n0], res [n0], status [n0][, P [n0, 16, 16] with want_P=True]) — views."""
+        dev = self._b.device
+        out = self._b.lqr(torch.as_tensor(A, device=dev).permute(1, 2, 0), torch.as_tensor(B, device=dev).permute(1, 2, 0), h_s, h_a, **kw)
+        return (out[0].permute(2, 0, 1),) + out[1:4] + tuple(x.permute(2, 0, 1) for x in out[4:])
+
     def get_extended_state(self):
         """nlplant(hstack(s,u)) — reference returns [n,17] with zero control derivatives (F16_model.py:47-49)."""
         d = self._b.derived()
