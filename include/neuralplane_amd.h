@@ -835,6 +835,56 @@ NP_STATIC_ASSERT(offsetof(np_f16_lqr_io, ld) == 16 && offsetof(np_f16_lqr_io, K)
 NP_STATIC_ASSERT(offsetof(np_f16_lqr_io, select) == 72 && offsetof(np_f16_lqr_io, max_doublings) == 76 && offsetof(np_f16_lqr_io, tol) == 88 && offsetof(np_f16_lqr_io, h_s) == 92 && offsetof(np_f16_lqr_io, h_a) == 140, "np_f16_lqr_io layout");
 int np_f16_model_lqr(np_f16_ctx *ctx, int64_t n, const np_f16_lqr_io *io, void *stream);
 
+/* Batched extended Kalman filter (a new symbol and record within ABI 16; no earlier record changes): for each of n rows `horizon` predict +
+ * update steps on the `update` step map (Euler, the F-16 nets), in ONE launch — the estimator that, beside np_f16_model_lqr's gains, makes
+ * LQG of noisy observations.  Coordinates are np_f16_ilqr_io's: x = (s[12], u[0:4]), u the lagged controls ENTERING the step; kappa and
+ * gain_k are the lag's factors, as in np_f16_lqr_io.  Per row and step t = 0 .. horizon - 1, from (s^, u^, P):
+ *   1. the mean:  u' = kappa u^ + gain_k clamp(a_t, -1, 1) (F16Model.update's expression);  xdot, A, B = np_f16_model_linearize's at (s^, u');
+ *         s- = s^ + dt xdot (update's Euler step);  x- = (s-, u').  u[4] passes through.  With every measurement absent s- and u' are
+ *         np_f16_model_rollout's (horizon 1) from the same start, bit for bit.
+ *   2. the covariance:  Phi = [[I + dt A, dt B], [0, I]],  S = diag(1 x 12, kappa x 4),  F = Phi S (the action is a known input: D does not
+ *         enter);  P- = sym(F P F^T) + diag(q[16]),  sym(M) = (M + M^T) / 2.
+ *   3. the update, in the form that shares np_f16_lqr_io's solve:  n_i = 1 / r[i] if bit i of `measure` is set and z_t[i] is finite, else 0
+ *         (a NaN or infinite z is a MISSING sample: sensor drop-outs and multi-rate sensors);  nu_i = z_t[i] - x-_i where n_i != 0, else 0;
+ *         W = I + P- N, N = diag(n);  P+ = sym(W^-1 P-) by Gauss-Jordan with partial pivoting;  x+ = x- + P+ (N nu);
+ *         nis_t = sum_i n_i nu_i (z_t[i] - x+_i), which is nu^T (C P- C^T + R)^-1 nu of the textbook form.  With no n_i non-zero the step
+ *         takes P+ = P-, x+ = x- to the bit and runs no solve.  Residuals are not wrapped: angles are the caller's business.
+ * Equilibration: the recursion runs in x = T x~, T = diag(2^rint(log2 scale[i])), exponents held to +-40, from the caller's 1-sigma
+ * magnitudes scale[16] (all ones = none): P~ = T^-1 P T^-1, F~ = T^-1 F T, q~ = q / t^2, n~ = n t^2 on entry, undone on every output;
+ * exact in fp32.  It only changes which pivots the solve takes; on the tests' inputs that lowers the covariance's fp32 error 24-fold
+ * (DESIGN section 22).  A pure function: nothing of the context is written.
+ *   inputs: s0 [12][ld0], u0 [5][ld0];  P0 [256][ld], plane 16 i + j;  actions with step and row strides as np_f16_ilqr_io's (step stride
+ *         0 = held);  z [horizon][16][ld] (planes without a bit in `measure` are never read; NULL with measure = 0).  HOST values: q[16] >= 0,
+ *         r[16] > 0 for the measured bits, measure (16 bits), scale[16] > 0, horizon >= 1, max_groups.
+ *   outputs: s_out [12][ld_out], u_out [5][ld_out], P_out [256][ld_out], status [n] (int32); optional (NULL = not wanted), per step:
+ *         x_traj [horizon][16][ld_out] the posterior means, pdiag_traj [horizon][16][ld_out] the posterior variances, nis [horizon][ld_out].
+ *   workspace: p_ws, n * 256 floats.
+ *   status: -1 the row ran through; otherwise the step t at which it STOPPED — a pivot of W was rejected (np_f16_lqr_io's rule: |p| <=
+ *         2^-20 of the largest element of its column) or P+ was not finite.  The final outputs of a stopped row are the estimate entering
+ *         step t; its per-step planes from t on are NaN.
+ *   A row whose x- or P- is not finite at step t — alpha, beta or el not finite, a NaN in P0, s0 or an action — has NaN final outputs
+ *         (u_out[4] still passes through), NaN per-step planes from t on and status -1, as its linearisation has.  Neighbours of a bad row
+ *         are untouched in every case.  The results do not depend on max_groups or on which rows share a launch.
+ *   chaining: horizon = H in one launch equals H launches of horizon = 1 fed their own outputs, bit for bit (rows that run through).
+ * Everything is checked on the host before the launch (np_last_error names the field).  Refused by name: an rk4 context, a context with a
+ * fleet, with aero_gemm_order, with aero_1d_tables, and a SingleCombat context.  cfg.airframe is honoured. */
+typedef struct np_f16_ekf_io {
+    const float *s0, *u0; int64_t ld0;          /* the prior mean: state [12][ld0], controls [5][ld0]; n rows */
+    const float *P0, *z; int64_t ld;            /* [256][ld]; [horizon][16][ld] */
+    const float *actions; int64_t act_step_stride, act_row_stride;   /* floats; step stride 0 = held */
+    float *s_out, *u_out, *P_out; int32_t *status;     /* [12][ld_out], [5][ld_out], [256][ld_out], [n] */
+    float *x_traj, *pdiag_traj, *nis; int64_t ld_out;  /* optional: [horizon][16][ld_out] twice, [horizon][ld_out] */
+    float *p_ws;                                /* n * 256 floats */
+    int32_t horizon, measure, max_groups, reserved_;   /* max_groups: 0 = auto; reserved_ must be 0 */
+    float q[16], r[16], scale[16];
+} np_f16_ekf_io;
+NP_STATIC_ASSERT(sizeof(np_f16_ekf_io) == 352, "np_f16_ekf_io is 352 bytes");
+NP_STATIC_ASSERT(offsetof(np_f16_ekf_io, ld0) == 16 && offsetof(np_f16_ekf_io, P0) == 24 && offsetof(np_f16_ekf_io, ld) == 40 && offsetof(np_f16_ekf_io, actions) == 48, "np_f16_ekf_io layout");
+NP_STATIC_ASSERT(offsetof(np_f16_ekf_io, s_out) == 72 && offsetof(np_f16_ekf_io, status) == 96 && offsetof(np_f16_ekf_io, x_traj) == 104 && offsetof(np_f16_ekf_io, ld_out) == 128, "np_f16_ekf_io layout");
+NP_STATIC_ASSERT(offsetof(np_f16_ekf_io, p_ws) == 136 && offsetof(np_f16_ekf_io, horizon) == 144 && offsetof(np_f16_ekf_io, measure) == 148 && offsetof(np_f16_ekf_io, max_groups) == 152, "np_f16_ekf_io layout");
+NP_STATIC_ASSERT(offsetof(np_f16_ekf_io, q) == 160 && offsetof(np_f16_ekf_io, r) == 224 && offsetof(np_f16_ekf_io, scale) == 288, "np_f16_ekf_io layout");
+int np_f16_model_ekf(np_f16_ctx *ctx, int64_t n, const np_f16_ekf_io *io, void *stream);
+
 /* Average duration in ms of the `count` most recent np_f16_step / np_f16_combat_step launches on this context, measured with
  * HIP events on the launch stream: a start / stop pair attached to each kernel's own dispatch (hipExtLaunchKernelGGL — the
  * timestamps of the kernel's packet, no extra barrier packets between back-to-back launches; 0 disables, enable with

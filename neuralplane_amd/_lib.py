@@ -204,6 +204,15 @@ class NpF16LqrIo(C.Structure):   # include/neuralplane_amd.h: np_f16_lqr_io
                 ('tol', C.c_float), ('h_s', C.c_float * 12), ('h_a', C.c_float * 4)]
 
 
+class NpF16EkfIo(C.Structure):   # include/neuralplane_amd.h: np_f16_ekf_io
+    _fields_ = [('s0', C.c_void_p), ('u0', C.c_void_p), ('ld0', C.c_int64), ('P0', C.c_void_p), ('z', C.c_void_p), ('ld', C.c_int64),
+                ('actions', C.c_void_p), ('act_step_stride', C.c_int64), ('act_row_stride', C.c_int64),
+                ('s_out', C.c_void_p), ('u_out', C.c_void_p), ('P_out', C.c_void_p), ('status', C.c_void_p),
+                ('x_traj', C.c_void_p), ('pdiag_traj', C.c_void_p), ('nis', C.c_void_p), ('ld_out', C.c_int64), ('p_ws', C.c_void_p),
+                ('horizon', C.c_int32), ('measure', C.c_int32), ('max_groups', C.c_int32), ('reserved_', C.c_int32),
+                ('q', C.c_float * 16), ('r', C.c_float * 16), ('scale', C.c_float * 16)]
+
+
 LQR_STATUS = {0: 'converged', 1: 'doubling limit', 3: 'pivot rejected', 4: 'non-finite'}
 TRIM_STATUS = {0: 'converged', 1: 'iteration limit', 2: 'line search stalled', 3: 'singular', 4: 'non-finite'}
 
@@ -245,7 +254,7 @@ def pack_kblob_gemm(blob):
 EXPORTS = ('np_abi_version', 'np_f16_airframe_default', 'np_f16_cache_floats', 'np_last_error', 'np_f16_ctx_create', 'np_f16_ctx_destroy', 'np_f16_reset',
            'np_f16_step', 'np_f16_derived', 'np_f16_aero_coefficients', 'np_f16_lowlevel_obs', 'np_f16_set_timing', 'np_f16_get_timing', 'np_f16_get_timing_samples', 'np_f16_set_trace', 'np_selfcheck_divc', 'np_selfcheck_math',
            'np_f16_combat_ctx_create', 'np_f16_combat_reset', 'np_f16_combat_step', 'np_f16_set_kernel_variant', 'np_actor_forward', 'np_rollout_returns', 'np_planning_inner_loop', 'np_planning_check', 'np_actor_pack_i8', 'np_rollout_insert', 'np_policy_act', 'np_planning_targets_obs', 'np_dispatch_plan', 'np_dispatch_plan_gemm', 'np_f16_pack_kblob_gemm',
-           'np_f16_set_fleet', 'np_f16_set_fleet_index', 'np_f16_model_rollout', 'np_f16_rollout_shape', 'np_f16_model_linearize', 'np_f16_linearize_groups', 'np_f16_model_rollout_vjp', 'np_f16_model_ilqr_backward', 'np_f16_model_rollout_feedback', 'np_f16_model_mppi', 'np_f16_model_trim', 'np_f16_model_lqr')
+           'np_f16_set_fleet', 'np_f16_set_fleet_index', 'np_f16_model_rollout', 'np_f16_rollout_shape', 'np_f16_model_linearize', 'np_f16_linearize_groups', 'np_f16_model_rollout_vjp', 'np_f16_model_ilqr_backward', 'np_f16_model_rollout_feedback', 'np_f16_model_mppi', 'np_f16_model_trim', 'np_f16_model_lqr', 'np_f16_model_ekf')
 KERNEL_VARIANTS = {'auto': 0, 'latency': 1, 'throughput': 2, 'pair': 3, 'latency8': 4, 'latency2': 5, 'latency4w': 6, 'dual8': 7, 'dual4': 8}
 
 _lib = None
@@ -310,6 +319,8 @@ def load():
         lib.np_f16_model_trim.argtypes = [C.c_void_p, C.c_int64, C.POINTER(NpF16TrimIo), C.c_void_p]
     if hasattr(lib, 'np_f16_model_lqr'):
         lib.np_f16_model_lqr.argtypes = [C.c_void_p, C.c_int64, C.POINTER(NpF16LqrIo), C.c_void_p]
+    if hasattr(lib, 'np_f16_model_ekf'):
+        lib.np_f16_model_ekf.argtypes = [C.c_void_p, C.c_int64, C.POINTER(NpF16EkfIo), C.c_void_p]
     lib.np_actor_forward.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_int, C.c_void_p]
     lib.np_planning_inner_loop.argtypes = [C.c_void_p, C.c_int64, C.POINTER(NpF16Io), C.POINTER(NpPlanningLoop), C.c_void_p]

@@ -17,8 +17,8 @@ SO = os.path.join(CSRC, 'libneuralplane_hip.so')
 SOURCES = ['np_env_t0s1.hip', 'np_env_t1s1.hip', 'np_env_t2s1.hip', 'np_env_t0s0.hip', 'np_env_t1s0.hip', 'np_env_t2s0.hip',
            'np_env_gemm_t0s1.hip', 'np_env_gemm_t1s1.hip', 'np_env_gemm_t2s1.hip', 'np_env_gemm_t0s0.hip', 'np_env_gemm_t1s0.hip', 'np_env_gemm_t2s0.hip',
            'np_env_fleet_t0s1.hip', 'np_env_fleet_t1s1.hip', 'np_env_fleet_t2s1.hip', 'np_env_fleet_t0s0.hip', 'np_env_fleet_t1s0.hip', 'np_env_fleet_t2s0.hip',
-           'np_f16_kernels.hip', 'np_planning.hip', 'np_combat_lat.hip', 'np_actor_i8.hip', 'np_policy.hip', 'np_model_rollout.hip', 'np_model_linearize.hip', 'np_model_rollout_vjp.hip', 'np_model_ilqr.hip', 'np_model_rollout_fb.hip', 'np_model_mppi.hip', 'np_model_trim.hip', 'np_model_lqr.hip']
-HEADERS = ['np_f16_device.h', 'np_f16_types.h', 'np_f16_host.h', 'np_f16_kargs.h', 'np_f16_env_kernel.h', 'np_f16_env_body.inc', 'np_env_launch.h', 'np_env_tu.inc', 'np_planning.h', 'np_model_rollout.h', 'np_model_linearize.h', 'np_model_jets.h', 'np_model_rollout_vjp.h', 'np_model_ilqr.h', 'np_model_rollout_fb.h', 'np_model_mppi.h', 'np_model_trim.h', 'np_model_lqr.h', 'np_dispatch.h', 'np_f16_combat.h', 'np_actor.h', 'np_actor_i8.h', 'np_rollout.h', 'np_policy.h', 'np_actor_asm.inc', 'np_actor_mfma_asm.inc', 'np_actor_mfma16_asm.inc', 'np_math.h', 'np_nets.h', 'np_mlp_asm.inc', 'np_mlp_asm_dual.inc', os.path.join('..', '..', 'include', 'neuralplane_amd.h')]
+           'np_f16_kernels.hip', 'np_planning.hip', 'np_combat_lat.hip', 'np_actor_i8.hip', 'np_policy.hip', 'np_model_rollout.hip', 'np_model_linearize.hip', 'np_model_rollout_vjp.hip', 'np_model_ilqr.hip', 'np_model_rollout_fb.hip', 'np_model_mppi.hip', 'np_model_trim.hip', 'np_model_lqr.hip', 'np_model_ekf.hip']
+HEADERS = ['np_f16_device.h', 'np_f16_types.h', 'np_f16_host.h', 'np_f16_kargs.h', 'np_f16_env_kernel.h', 'np_f16_env_body.inc', 'np_env_launch.h', 'np_env_tu.inc', 'np_planning.h', 'np_model_rollout.h', 'np_model_linearize.h', 'np_model_jets.h', 'np_model_rollout_vjp.h', 'np_model_ilqr.h', 'np_model_rollout_fb.h', 'np_model_mppi.h', 'np_model_trim.h', 'np_model_lqr.h', 'np_model_mat16.h', 'np_model_ekf.h', 'np_dispatch.h', 'np_f16_combat.h', 'np_actor.h', 'np_actor_i8.h', 'np_rollout.h', 'np_policy.h', 'np_actor_asm.inc', 'np_actor_mfma_asm.inc', 'np_actor_mfma16_asm.inc', 'np_math.h', 'np_nets.h', 'np_mlp_asm.inc', 'np_mlp_asm_dual.inc', os.path.join('..', '..', 'include', 'neuralplane_amd.h')]
 # -disable-machine-licm: the SingleCombat kernel's inner loop (5 FDM steps) otherwise gets ~40 loop-invariant 64-bit constants of the
 # fp64 sin / cos / pow sequences hoisted into VGPR pairs that stay live across the asm phases — 256 VGPRs plus 9 spilled dwords;
 # re-materialised inside the loop it needs 200 and no scratch (the other kernels have no loops and compile identically)
@@ -33,6 +33,7 @@ SOURCE_FLAGS = {'np_model_rollout.hip': ['-fno-slp-vectorize'], 'np_model_linear
                 'np_model_rollout_fb.hip': ['-fno-slp-vectorize'],   # the feedback rollout: as the open-loop rollout
                 'np_model_mppi.hip': ['-fno-slp-vectorize'],         # the MPPI step: as the open-loop rollout (its packed Box-Muller is spelled out)
                 'np_model_trim.hip': ['-fno-slp-vectorize'],         # the trim solve: as the linearisation, whose passes it runs
+                'np_model_ekf.hip': ['-fno-slp-vectorize'],          # the filter: as the linearisation, whose passes it runs
                 'np_model_rollout_vjp.hip': ['-fno-slp-vectorize', '-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops'],
                 'np_model_ilqr.hip': ['-fno-slp-vectorize', '-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']}   # the Riccati sweep: as the reverse sweep
 OBJ_DIR = os.path.join(CSRC, 'build')

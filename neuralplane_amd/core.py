@@ -670,6 +670,68 @@ class F16Batch:
         _lib.check(self.lib.np_f16_model_lqr(self._ctx, n0, C.byref(io), self._stream()))
         return (K, doublings, res, status) + ((P,) if want_P else ())
 
+    def ekf(self, actions, z, P, q, r, measure, s=None, u=None, scale=None, horizon=None, want_traj=False, max_groups=0, ld_out=None):
+        """Batched extended Kalman filter: H predict + update steps of the update() step map per row in ONE launch (np_f16_model_ekf; Euler
+        only) — the estimator beside lqr's gains.  x = (s[12], u[0:4]), the coordinates of ilqr_backward and lqr.  Per step the mean goes
+        through update() itself (with no measurement it is rollout's, bit for bit), the covariance through the step Jacobian of linearize at
+        the current estimate plus diag(q), and the measurement z_t of the coordinates in the 16-bit mask `measure`, with variances r, is
+        folded in by P+ = sym((I + P- N)^-1 P-), x+ = x- + P+ N (z - x-), N = diag(1 / r) over the samples that are there: a NaN in z is a
+        missing sample (a drop-out, a slower sensor).  Angle residuals are not wrapped.
+        actions [H, n0, >=4], or [n0, >=4] with horizon=H for one action held; z [H, 16, n0] planar (None with measure = 0; planes outside
+        `measure` are never read); P [16, 16, n0] the prior covariance; q [16], r [16] host values; s [12, n0], u [5, n0] the prior mean
+        (both or neither: omitted = the batch's current state); scale [16]: 1-sigma magnitudes for the solve's equilibration (None = ones).
+        Returns (s [12, n0], u [5, n0], P [16, 16, n0], status [n0] int32: -1, or the step at which the row stopped with the estimate it
+        had — a rejected pivot or a non-finite P+ —)[, with want_traj: x_traj [H, 16, n0] the posterior means, pdiag_traj [H, 16, n0] the
+        posterior variances, nis [H, n0] the normalised innovation squared, whose expectation is the number of samples of the step].
+        A row with a non-finite estimate returns NaN.  A pure function, as rollout; H steps equal H chained calls of one step, bit for bit.
+        The planar outputs are sliced out of [.., ld_out] allocations when ld_out > n0."""
+        if (s is None) != (u is None):
+            raise ValueError('ekf: s and u come together (or neither: the prior mean is the batch\'s current state)')
+        if s is None:
+            s, u = self.s, self.u
+        if s.dim() != 2 or u.dim() != 2 or s.shape[0] != 12 or u.shape[0] != 5 or s.shape[1] != u.shape[1] or s.shape[1] < 1:
+            raise ValueError(f'ekf: s must be [12, n0] and u [5, n0], got {tuple(s.shape)} and {tuple(u.shape)}')
+        f32 = dict(device=self.device, dtype=torch.float32)
+        s, u = s.to(**f32).contiguous(), u.to(**f32).contiguous()
+        n0, measure = int(s.shape[1]), int(measure)
+        actions = torch.as_tensor(actions).to(**f32).contiguous()
+        if actions.dim() not in (2, 3) or (actions.dim() == 2 and horizon is None):
+            raise ValueError(f'ekf: actions must be [H, n0, >=4], or [n0, >=4] with horizon=H, got {tuple(actions.shape)}')
+        held, h = actions.dim() == 2, int(horizon if actions.dim() == 2 else actions.shape[0])
+        if horizon is not None and int(horizon) != h:
+            raise ValueError(f'ekf: horizon={horizon} but the action sequence has {h} steps')
+        if actions.shape[-2] != n0 or actions.shape[-1] < 4:
+            raise ValueError(f'ekf: actions must have n0 = {n0} rows of >= 4 columns, got {tuple(actions.shape)}')
+        if tuple(P.shape) != (16, 16, n0):
+            raise ValueError(f'ekf: P must be [16, 16, n0 = {n0}], got {tuple(P.shape)}')
+        P = P.to(**f32).contiguous()
+        if z is not None:
+            if tuple(z.shape) != (h, 16, n0):
+                raise ValueError(f'ekf: z must be [H, 16, n0] = {(h, 16, n0)}, got {tuple(z.shape)}')
+            z = z.to(**f32).contiguous()
+        io = _lib.NpF16EkfIo()
+        for name, given in (('q', q), ('r', r), ('scale', [1.0] * 16 if scale is None else scale)):
+            vals = [float(x) for x in torch.as_tensor(given).reshape(-1).tolist()]
+            if len(vals) != 16:
+                raise ValueError(f'ekf: {name} must have 16 entries, got {len(vals)}')
+            setattr(io, name, (C.c_float * 16)(*vals))
+        ld_out = n0 if ld_out is None else int(ld_out)
+        lo = max(ld_out, 1)
+        io.s0, io.u0, io.ld0, io.P0, io.z, io.ld = s.data_ptr(), u.data_ptr(), n0, P.data_ptr(), (None if z is None else z.data_ptr()), n0
+        io.actions, io.act_row_stride, io.act_step_stride = actions.data_ptr(), actions.stride(-2), (0 if held or h <= 1 else actions.stride(0))
+        io.horizon, io.measure, io.max_groups = h, measure, int(max_groups)
+        s_out, u_out, P_out = (torch.empty((k, lo), **f32) for k in (12, 5, 256))
+        status = torch.empty(n0, dtype=torch.int32, device=self.device)
+        p_ws = torch.empty((n0, 256), **f32)
+        io.s_out, io.u_out, io.P_out, io.status, io.ld_out, io.p_ws = s_out.data_ptr(), u_out.data_ptr(), P_out.data_ptr(), status.data_ptr(), ld_out, p_ws.data_ptr()
+        traj = ()
+        if want_traj:
+            traj = tuple(torch.empty((max(h, 1), k, lo), **f32) for k in (16, 16, 1))
+            io.x_traj, io.pdiag_traj, io.nis = (x.data_ptr() for x in traj)
+        _lib.check(self.lib.np_f16_model_ekf(self._ctx, n0, C.byref(io), self._stream()))
+        out = (s_out[:, :n0], u_out[:, :n0], P_out.view(16, 16, lo)[..., :n0], status)
+        return out + tuple(x[..., :n0] for x in traj[:2]) + tuple(x[:, 0, :n0] for x in traj[2:])
+
     def rollout_vjp(self, actions, s_traj, g_s_traj, g_u_end=None, s=None, u=None, fanout=1, horizon=None, max_groups=0, ld_out=None):
         """The vector-Jacobian product of rollout(actions, s, u, fanout, record_every=1) as ONE launch (np_f16_model_rollout_vjp; Euler only):
         with cotangents g_s_traj [H, 12, n0 * fanout] on the recorded states s_traj and g_u_end [5, n0 * fanout] (None = zero) on u_end,

@@ -607,6 +607,58 @@ inline void lqr_equilibration(const np_f16_lqr_io *io, const float (&gain)[4], f
     }
 }
 
+// ---- np_f16_model_ekf (np_model_ekf.hip) -----------------------------------------------------------------------------------------------
+// The record of a filter run over n rows, checked before anything is launched: null, or the first thing wrong with it.  q, r, scale and
+// measure are host values inside the record.  The row limits are the linearisation's and the rollout's (a row of the actions is a 64-bit
+// base + a 32-bit byte offset); the grid is linearize_groups of n rows.
+inline const char *ekf_io_error(int64_t n, const np_f16_ekf_io *io) {
+    if (!io) return "np_f16_model_ekf: null io";
+    const int64_t lim = 1ll << 30;
+    if (n < 1 || n >= lim) return "np_f16_model_ekf: n must be at least 1 and below 2^30";
+    if (io->horizon < 1) return "np_f16_model_ekf: horizon must be at least 1";
+    if (io->measure < 0 || io->measure > 0xFFFF) return "np_f16_model_ekf: measure must be a mask of the 16 coordinates";
+    for (int i = 0; i < 16; i++) {
+        if (!(io->q[i] >= 0.0f) || !(io->q[i] - io->q[i] == 0.0f)) return "np_f16_model_ekf: q must be finite and not negative";
+        if (((io->measure >> i) & 1) && (!(io->r[i] > 0.0f) || !(io->r[i] - io->r[i] == 0.0f))) return "np_f16_model_ekf: r must be finite and positive for every measured coordinate";
+        if (!(io->scale[i] > 0.0f) || !(io->scale[i] - io->scale[i] == 0.0f)) return "np_f16_model_ekf: scale must be finite and positive";
+    }
+    if (!io->s0 || !io->u0 || !io->P0) return "np_f16_model_ekf: null prior (s0, u0, P0)";
+    if (!io->actions) return "np_f16_model_ekf: null actions";
+    if (io->measure != 0 && !io->z) return "np_f16_model_ekf: null measurements (z) with a non-zero measure";
+    if (!io->s_out || !io->u_out || !io->P_out || !io->status) return "np_f16_model_ekf: null output (s_out, u_out, P_out, status)";
+    if (!io->p_ws) return "np_f16_model_ekf: null workspace (p_ws)";
+    if (io->ld0 < n || io->ld0 >= lim) return "np_f16_model_ekf: ld0 must be at least n and below 2^30";
+    if (io->ld < n || io->ld >= lim) return "np_f16_model_ekf: ld must be at least n and below 2^30";
+    if (io->ld_out < n || io->ld_out >= lim) return "np_f16_model_ekf: ld_out must be at least n and below 2^30";
+    if (io->act_row_stride < 4 || io->act_row_stride >= lim || n * io->act_row_stride >= lim)
+        return "np_f16_model_ekf: act_row_stride must be at least 4 floats, and n * act_row_stride below 2^30";
+    if (io->act_step_stride != 0 && io->act_step_stride < (n - 1) * io->act_row_stride + 4)
+        return "np_f16_model_ekf: act_step_stride must be 0 (a held action) or cover the n action rows of a step";
+    if (io->max_groups < 0) return "np_f16_model_ekf: max_groups must not be negative";
+    if (io->reserved_ != 0) return "np_f16_model_ekf: reserved_ must be 0";
+    return nullptr;
+}
+
+// Contexts the filter kernel is not built for: null, or the refusal, by name
+inline const char *ekf_context_error(bool combat, bool fleet, bool gemm_order, bool tables, int32_t solver) {
+    if (combat) return "np_f16_model_ekf: a SingleCombat context has no model kernels (create the context with np_f16_ctx_create)";
+    if (fleet) return "np_f16_model_ekf: a context with a fleet has no filter (it reads one airframe per context)";
+    if (gemm_order) return "np_f16_model_ekf: a context with aero_gemm_order has no filter (built for the default order of the aero nets)";
+    if (tables) return "np_f16_model_ekf: a context with aero_1d_tables has no filter (built for the MLP numerics)";
+    if (solver != 0) return "np_f16_model_ekf: solver: rk4 has no filter (the step map is the Euler step's)";
+    return nullptr;
+}
+
+// The equilibration x = T x~ of np_f16_ekf_io: t[16] and 1 / t, powers of two with exponents in [-40, 40]
+inline void ekf_equilibration(const np_f16_ekf_io *io, float (&t)[16], float (&tinv)[16]) {
+    for (int i = 0; i < 16; i++) {
+        double e = std::nearbyint(std::log2((double)io->scale[i]));
+        e = e < -40.0 ? -40.0 : (e > 40.0 ? 40.0 : e);
+        t[i] = (float)std::exp2(e);
+        tinv[i] = (float)std::exp2(-e);
+    }
+}
+
 // ---- np_f16_model_rollout_vjp (np_model_rollout_vjp.hip) ----------------------------------------------------------------------------
 // The record of a reverse sweep over n0 start rows, checked before anything is launched: null, or the first thing wrong with it.  The
 // limits are the rollout's (rows of every array are a 64-bit base + a 32-bit byte offset); the grid is linearize_groups of n0 * fanout rows.

@@ -37,6 +37,7 @@
 #include "np_model_mppi.h"
 #include "np_model_trim.h"
 #include "np_model_lqr.h"
+#include "np_model_ekf.h"
 namespace npact8 {
 hipError_t launch_actor_i8(const float *weights, long long n, const float *obs, const float *h_in, const float *masks, float *actions, float *h_out,
                            hipStream_t stream);   // np_actor_i8.hip
@@ -1755,6 +1756,39 @@ int np_f16_model_lqr(np_f16_ctx *ctx, int64_t n, const np_f16_lqr_io *io, void *
     }
     for (int i = 0; i < 16; i++) a.q[i] = (i < 12 && ((io->select >> i) & 1)) ? (io->h_s[i] * a.t[i]) * a.t[i] : 0.0f;
     NP_HIP(launch_model_lqr(lqr_groups(n, ctx->num_cus, io->max_groups), a, (hipStream_t)stream));
+    return 0;
+}
+
+// The batched extended Kalman filter in one launch (np_model_ekf.hip).  As its siblings: the record first, then the context; nothing is
+// touched, and no device call is made, before every refusal has had its turn.  The noise levels, the sensor mask and the equilibration travel in the
+// kernel's argument record.
+int np_f16_model_ekf(np_f16_ctx *ctx, int64_t n, const np_f16_ekf_io *io, void *stream) {
+    if (const char *e = ekf_io_error(n, io)) return fail(e);
+    if (!ctx) return fail("np_f16_model_ekf: null ctx");
+    if (const char *e = ekf_context_error(ctx->combat, ctx->fleet_k > 0, ctx->gemm_order, !ctx->combat && ctx->cfg.aero_1d_tables != 0, ctx->solver)) return fail(e);
+    int32_t groups = 0;
+    if (const char *e = linearize_groups(n, ctx->num_cus, io->max_groups, &groups)) return fail(e);
+    DeviceGuard guard;
+    NP_HIP(guard.enter(ctx->device));
+    EkfArgs a;
+    a.s0 = io->s0; a.u0 = io->u0; a.ld0 = io->ld0;
+    a.P0 = io->P0; a.z = io->z; a.ld = io->ld;
+    a.actions = io->actions; a.act_step_stride = io->horizon > 1 ? io->act_step_stride : 0; a.act_row_stride = io->act_row_stride;
+    a.s_out = io->s_out; a.u_out = io->u_out; a.P_out = io->P_out; a.status = io->status;
+    a.x_traj = io->x_traj; a.pdiag_traj = io->pdiag_traj; a.nis = io->nis; a.ld_out = io->ld_out;
+    a.p_ws = io->p_ws;
+    a.rows = n;
+    a.horizon = io->horizon; a.measure = io->measure;
+    a.dt = ctx->cfg.dt; a.kappa = ctx->cfg.af.lag_keep;
+    ekf_equilibration(io, a.t, a.tinv);
+    for (int i = 0; i < 16; i++) {
+        a.q[i] = (io->q[i] * a.tinv[i]) * a.tinv[i];
+        a.rinv[i] = ((io->measure >> i) & 1) ? 1.0f / io->r[i] : 0.0f;
+        a.nt[i] = (a.rinv[i] * a.t[i]) * a.t[i];
+    }
+    a.kblob = ctx->wt.kblob;
+    a.af = ctx->cfg.af;
+    NP_HIP(launch_model_ekf(groups, a, (hipStream_t)stream));
     return 0;
 }
 

@@ -29,10 +29,11 @@
 #include "np_model_lqr.h"
 
 #include "np_f16_device.h"
+#include "np_model_mat16.h"
 
 namespace npf16 {
 
-constexpr int LQR_IN_PLANES = 192, LQR_IN_STRIDE = 193, LQR_OUT_PLANES = 64 + 256, LQR_OUT_STRIDE = 321, LQR_SYM_STRIDE = 17;
+constexpr int LQR_IN_PLANES = 192, LQR_IN_STRIDE = 193, LQR_OUT_PLANES = 64 + 256, LQR_OUT_STRIDE = 321, LQR_SYM_STRIDE = mat16::SYM_STRIDE;
 constexpr int LQR_LDS_FLOATS = LQR_TILE * (LQR_IN_STRIDE + LQR_OUT_STRIDE) + LQR_WAVES * 16 * LQR_SYM_STRIDE;
 static_assert(LQR_LDS_FLOATS * sizeof(float) <= 40 * 1024, "at least two workgroups per CU");
 static_assert(LQR_TILE == 4 * LQR_WAVES, "a wave solves four rows of the tile");
@@ -41,42 +42,7 @@ typedef const LqrArgs __attribute__((address_space(4))) *LqrArgsC;
 
 namespace lqr {
 
-// LDS traffic between the lanes of ONE wave: the DS instructions of a wave execute in order; this keeps the compiler from reordering them
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-template <class T>
-__device__ __forceinline__ __attribute__((address_space(1))) T *glob(T *p) {
-    return reinterpret_cast<__attribute__((address_space(1))) T *>(reinterpret_cast<uintptr_t>(p));
-}
-__device__ __forceinline__ float lane_get(float v, int lane) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane)); }
-__device__ __forceinline__ float from_lane(float v, int lane) { return __int_as_float(__builtin_amdgcn_ds_bpermute(lane * 4, __float_as_int(v))); }
-__device__ __forceinline__ float pick4(int i, const f32x4 &x) { return i == 0 ? x[0] : i == 1 ? x[1] : i == 2 ? x[2] : x[3]; }
-__device__ __forceinline__ bool finite4(const f32x4 &x) { return ((x[0] - x[0]) + (x[1] - x[1])) + ((x[2] - x[2]) + (x[3] - x[3])) == 0.0f; }
-__device__ __forceinline__ bool wave_any(bool b) { return __builtin_amdgcn_ballot_w64(b) != 0; }
-
-// X^T Y in the accumulator layout: the k index runs in the accumulator's order, so neither operand is shuffled
-__device__ __forceinline__ f32x4 mm(const f32x4 &X, const f32x4 &Y) {
-    f32x4 C = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-    for (int r = 0; r < 4; r++) C = __builtin_amdgcn_mfma_f32_16x16x4f32(X[r], Y[r], C, 0, 0, 0);
-    return C;
-}
-
-// 1/2 (M + M^T) through the wave's transpose area
-__device__ __forceinline__ f32x4 sym_half(const f32x4 &M, float *scr, int g, int c) {
-    f32x4 out;
-    wave_sync();
-#pragma unroll
-    for (int r = 0; r < 4; r++) scr[(4 * g + r) * LQR_SYM_STRIDE + c] = M[r];
-    wave_sync();
-#pragma unroll
-    for (int r = 0; r < 4; r++) out[r] = 0.5f * (M[r] + scr[c * LQR_SYM_STRIDE + 4 * g + r]);
-    wave_sync();
-    return out;
-}
+using namespace mat16;   // the product, the symmetrisation, the solve and the lane helpers (np_model_mat16.h)
 
 // entry (i, j) of the equilibrated A_d = T^-1 M Phi S M T from the row's record `in` (A as [12][12], then B as [12][4])
 __device__ __forceinline__ float a_d(const float *in, LqrArgsC ap, int i, int j) {
@@ -90,47 +56,6 @@ __device__ __forceinline__ float b_d(const float *in, LqrArgsC ap, int i, int k)
     float phi = i == 12 + k ? 1.0f : 0.0f;
     if (i < 12) phi = phi + ap->dt * in[144 + i * 4 + k];
     return (((float)((ap->select >> i) & 1) * phi) * ap->gain[k]) * ap->tinv[i];
-}
-
-// Gauss-Jordan with partial pivoting on [W | X | Y], rows left in place: on return row p_k of X, Y holds row k of W^-1 [X | Y] and
-// PT[r] = 1 where p_c = 4 g + r.  0 = done, 1 = a pivot was rejected, 2 = a pivot was NaN
-__device__ __forceinline__ int solve(f32x4 &W, f32x4 &X, f32x4 &Y, f32x4 &PT, int g, int c) {
-    float cmax = fmaxf(fmaxf(fabsf(W[0]), fabsf(W[1])), fmaxf(fabsf(W[2]), fabsf(W[3])));
-    cmax = fmaxf(cmax, from_lane(cmax, (16 * g + c) ^ 16));
-    cmax = fmaxf(cmax, from_lane(cmax, (16 * g + c) ^ 32));   // the largest |W_ic| of the lane's column
-    unsigned used = 0;
-    PT = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-    for (int k = 0; k < 16; k++) {
-        unsigned key = 0;
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const int row = 4 * g + r;
-            const unsigned cand = (__float_as_uint(fabsf(W[r])) & ~15u) | (unsigned)(15 - row);
-            key = max(key, ((used >> row) & 1u) ? 0u : cand);
-        }
-        const unsigned k0 = __builtin_amdgcn_readlane(key, k), k1 = __builtin_amdgcn_readlane(key, 16 + k);
-        const unsigned k2 = __builtin_amdgcn_readlane(key, 32 + k), k3 = __builtin_amdgcn_readlane(key, 48 + k);
-        const int p = 15 - (int)(max(max(k0, k1), max(k2, k3)) & 15u);   // wave-uniform
-        const int gp = p >> 2, rp = p & 3;
-        const float piv = lane_get(pick4(rp, W), 16 * gp + k);
-        if (!(fabsf(piv) > 0x1p-20f * lane_get(cmax, k))) return piv != piv ? 2 : 1;
-        const float rw = from_lane(pick4(rp, W), 16 * gp + c) / piv, rx = from_lane(pick4(rp, X), 16 * gp + c) / piv;
-        const float ry = from_lane(pick4(rp, Y), 16 * gp + c) / piv;
-        float mult[4];
-#pragma unroll
-        for (int r = 0; r < 4; r++) mult[r] = from_lane(W[r], 16 * g + k);
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const bool is_p = 4 * g + r == p;
-            W[r] = is_p ? rw : fmaf(-mult[r], rw, W[r]);
-            X[r] = is_p ? rx : fmaf(-mult[r], rx, X[r]);
-            Y[r] = is_p ? ry : fmaf(-mult[r], ry, Y[r]);
-            if (c == k) PT[r] = is_p ? 1.0f : 0.0f;
-        }
-        used |= 1u << p;
-    }
-    return 0;
 }
 
 // Qt = L diag(piv) L^T, unit lower L, row by row in this fixed order; x = -Qt^-1 b (np_model_ilqr.hip)

@@ -155,6 +155,16 @@ class F16Model(BaseModel):
         out = self._b.lqr(torch.as_tensor(A, device=dev).permute(1, 2, 0), torch.as_tensor(B, device=dev).permute(1, 2, 0), h_s, h_a, **kw)
         return (out[0].permute(2, 0, 1),) + out[1:4] + tuple(x.permute(2, 0, 1) for x in out[4:])
 
+    def ekf(self, actions, z, P, q, r, measure, s=None, u=None, **kw):
+        """Batched extended Kalman filter — H predict + update steps of update() per aircraft in ONE kernel launch (F16Batch.ekf,
+        np_f16_model_ekf; Euler only), in this class's row-major layout: actions [H, n0, >=4], z [H, n0, 16] (NaN = a missing sample),
+        P [n0, 16, 16], s [n0, 12], u [n0, 5] (default: the current state).  This model's s / u / recent_* are left exactly as they were.
+        Returns (s [n0, 12], u [n0, 5], P [n0, 16, 16], status [n0][, x_traj [H, n0, 16], pdiag_traj [H, n0, 16], nis [H, n0] with
+        want_traj=True]) — views."""
+        t = lambda x: None if x is None else torch.as_tensor(x, device=self._b.device).transpose(-1, -2)  # noqa: E731
+        out = self._b.ekf(actions, t(z), torch.as_tensor(P, device=self._b.device).permute(1, 2, 0), q, r, measure, s=t(s), u=t(u), **kw)
+        return (out[0].t(), out[1].t(), out[2].permute(2, 0, 1), out[3]) + tuple(x.transpose(1, 2) for x in out[4:6]) + out[6:]
+
     def get_extended_state(self):
         """nlplant(hstack(s,u)) — reference returns [n,17] with zero control derivatives (F16_model.py:47-49)."""
         d = self._b.derived()
